@@ -60,6 +60,19 @@ int tsim_update_model(tsim_batch* b, const int32_t* I, const double* F, void* st
 int tsim_set_env_tables(tsim_batch* b, const void* tables, void* stream);
 int tsim_table_size(const tsim_batch* b);
 
+/* backward_info.flag_p / backward_results.df_dp (envs/redmax_torch_functions.py:83,151), batched, for the physical parameters
+ * of the numeric tables: while dL_dtables (DEVICE [B][tsim_table_size], the batch's real type) is set, every tsim_backward_steps /
+ * tsim_backward_episode ADDS dL/d(row entry) for the entries tsim_model_table_offset names (pair kn kt mu damping, sensor kn kt mu
+ * damping, dof damping) and leaves every other entry untouched.  NULL = off.  No host synchronisation.
+ * Per environment: dL/dp = sum over the undone sub-steps t of -(dg_t/dp)^T z_t (g_t = r_t / ca_t the scaled residual, z_t the adjoint
+ * solution of the sub-step) + the direct term of the seeded tactile frames (sensor parameters).  The adjoint launch then saves z of every
+ * sub-step (the same kernel variant, compiled with that store) and a second pass over (environment, chunk of sub-steps) adds the gradient;
+ * sums are in a fixed order (bit-identical from run to run).  The entries are those of the environment's row of tsim_set_env_tables, or of
+ * the shared model.  The stick / slip switch of the friction law is a kink: these are one-sided derivatives of the smooth piece each contact
+ * point is on (tsim_debug_signature).  The first non-NULL call allocates [tape_capacity][B][ndof_r] reals for z.  Not available on the fused
+ * closed-loop launches (tsim_push_closed_backward fails while it is set). */
+int tsim_set_param_grad(tsim_batch* b, void* dL_dtables);
+
 /* sim.set_state_init(q, qdot) + sim.reset(backward_flag)      envs/redmax_torch_functions.py:39-41,
  * envs/tactile_push_env.py:138,154.  q0 / qd0: [B][ndof_r].  Restarts the tape and zeroes the carried
  * adjoint. */

@@ -644,8 +644,12 @@ __device__ __forceinline__ R prim_distance(int prim, const R* shape, V3<R> x) {
   return t_max(t_sqrt(x.x * x.x + x.y * x.y) - shape[0], t_abs(x.z) - shape[1]);        // cylinder: inside iff both are negative
 }
 
+// geo (the parameter gradient, csrc/tsim_param_grad.hip): the quantities of the law at this point that its derivative w.r.t. (kn, kt, mu, kd)
+// needs — written only for a penetrating point; null at every other call site.
+template <class R> struct ContactGeo { R d, dd, fn, vtn, sg; V3<R> n, vt; bool stick; };
 template <class R, bool JAC>
-__device__ __forceinline__ bool contact_law(int prim, const R* shape, const R* kp, V3<R> x, V3<R> v, V3<R>& F, M3<R>& Jx, M3<R>& Jv, V3<double> xh, int* branch = nullptr, bool jac = true) {
+__device__ __forceinline__ bool contact_law(int prim, const R* shape, const R* kp, V3<R> x, V3<R> v, V3<R>& F, M3<R>& Jx, M3<R>& Jv, V3<double> xh, int* branch = nullptr, bool jac = true,
+                                            ContactGeo<R>* geo = nullptr) {
   const R kn = kp[0], kt = kp[1], mu = kp[2], kd = kp[3];
   R d; V3<R> n;
   R ncurv = R(0);          // N = dn/dx = ncurv * (Pm - n n^T), Pm = diag(1, 1, pz)
@@ -681,6 +685,7 @@ __device__ __forceinline__ bool contact_law(int prim, const R* shape, const R* k
   const R sg = fn >= R(0) ? R(1) : R(-1);
   if (!stick) s = mu * sg * fn / vtn;
   F = n * fn - vt * s;
+  if (geo) { geo->d = d; geo->dd = dd; geo->fn = fn; geo->vtn = vtn; geo->sg = sg; geo->n = n; geo->vt = vt; geo->stick = stick; }
   if (JAC && jac) {      // jac: a wave-uniform run-time switch on top (value-only evaluations of line-search trials, evaluate())
     // N w = ncurv (Pm w - n (n.w))
     const V3<R> Nv = (mk3<R>(v.x, v.y, pz * v.z) - n * dd) * ncurv;
@@ -711,4 +716,19 @@ __device__ __forceinline__ bool contact_law(int prim, const R* shape, const R* k
       }
   }
   return true;
+}
+
+// dF / d(kn, kt, mu, kd) of contact_law at a penetrating point, from what it left in geo (fn = (-kn + kd dd) d, F = n fn - vt s,
+// s = kt sticking, mu sg fn / |vt| slipping).  One-sided on the stick / slip kink: the derivative of the piece the point is on.
+template <class R> __device__ __forceinline__ void contact_law_dparam(const ContactGeo<R>& g, const R* kp, V3<R> (&dF)[4]) {
+  const R mu = kp[2];
+  dF[0] = g.n * (-g.d); dF[3] = g.n * (g.dd * g.d);
+  if (g.stick) { dF[1] = g.vt * R(-1); dF[2] = zero3<R>(); }
+  else {
+    const R c = mu * g.sg / g.vtn;                 // ds / dfn
+    dF[0] = dF[0] + g.vt * (c * g.d);              // -vt ds/dkn = -vt c (-d)
+    dF[3] = dF[3] - g.vt * (c * g.dd * g.d);
+    dF[1] = zero3<R>();
+    dF[2] = g.vt * (-g.sg * g.fn / g.vtn);
+  }
 }

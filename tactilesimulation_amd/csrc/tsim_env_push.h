@@ -221,6 +221,7 @@ extern "C" int tsim_push_closed_backward(tsim_batch* b, const tsim_push_policy* 
                                          const void* df_dq, const void* df_dvar, const void* du_direct, const void* u_out, const void* h1_out, const void* h2_out,
                                          void* g1_out, void* g2_out, void* g3_out, void* dobs_tac, void* df_du, void* stream) {
   if (int rc = push_closed_check(b, pol, num_frames, num_steps, "push_closed_backward")) return rc;
+  if (b->dLdp) return fail("push_closed_backward: the parameter gradient (tsim_set_param_grad) is not available on the fused closed-loop launches; set it to NULL");
   if (!pol->W1p || !pol->W2 || pol->w1_stride < push_obs_len(pol->obs_mode) || pol->w1_stride % 4 || pol->w1_stride > 64 * (int)PP_OCH) return fail("push_closed_backward: W1p [64][w1_stride >= observation length, multiple of 4] and W2 are required");
   if (!b->record) return fail("push_closed_backward: reset(backward_flag=True) was not called");
   const long long n = (long long)num_frames * num_steps;

@@ -25,6 +25,7 @@
 
 
 #include "tsim_kernels.h"
+#include "tsim_param_grad.h"
 
 // ================================================================================================ LPT ordering
 // One block: counting sort of the environments by their residual-evaluation count of the last launch, descending
@@ -454,6 +455,9 @@ struct tsim_batch {
   std::vector<void*> pool;          // spare tape buffers
   std::vector<void*> retired;       // per-frame pose records replaced by larger ones while a captured graph may still name them (launch_forward)
   long long* bwd_stamps = nullptr;  // diagnostics (tsim_debug_stamps)
+  // tsim_set_param_grad: the caller's table gradient [B][nfrec] (null: off), the adjoint solutions z [cap][B][nr] the adjoint launch saves for the
+  // parameter pass, and that pass's partial sums [pg_chunks][B][ts_pg_count] (both allocated when the gradient is first asked for)
+  void* dLdp = nullptr; void* zbuf = nullptr; void* pgpart = nullptr; int pg_chunks = 0;
   // tsim_kernel_timing: HIP events around every launch of the simulation kernels, on the stream they are launched on
   int kt_on = 0;
   std::vector<KtPair> kt;           // pairs recorded since the last tsim_kernel_times
@@ -770,23 +774,29 @@ void ts_static_pusher_launch(const FwdArgs<double>& a, int lpe, unsigned grid, s
 void ts_static_pusher_launch(const BwdArgs<double>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
 void ts_param_pusher_launch(const FwdArgs<double>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
 void ts_param_pusher_launch(const BwdArgs<double>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
+// ... and the SAVEZ twins of their adjoint kernels (tsim_set_param_grad: z of every sub-step saved for the parameter pass)
+void ts_static_pusher_launch(const BwdArgs<float>& a, float* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st);
+void ts_static_pusher_launch(const BwdArgs<double>& a, double* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st);
+void ts_param_pusher_launch(const BwdArgs<float>& a, float* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st);
+void ts_param_pusher_launch(const BwdArgs<double>& a, double* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st);
 // kernel variants: NRM = 8 / 16 rows in the register solve; EXPJ = model has a rotation-vector joint (its code is
 // compiled out otherwise: it costs registers in every evaluation); LPE as above
-#define TS_LAUNCH_L(KERNEL, R, NRM, L, st, a) do {                                                                       \
-    if (L.lpe == 64) hipLaunchKernelGGL((KERNEL<R, NRM, false, 64>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);         \
-    else if (L.lpe == 32) hipLaunchKernelGGL((KERNEL<R, NRM, false, 32>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);    \
-    else hipLaunchKernelGGL((KERNEL<R, NRM, false, 16>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);                     \
+// (variadic: the kernel's arguments — k_backward_z, the SAVEZ twin of k_backward, takes the z buffer as a second one)
+#define TS_LAUNCH_L(KERNEL, R, NRM, L, st, ...) do {                                                                     \
+    if (L.lpe == 64) hipLaunchKernelGGL((KERNEL<R, NRM, false, 64>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);         \
+    else if (L.lpe == 32) hipLaunchKernelGGL((KERNEL<R, NRM, false, 32>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);    \
+    else hipLaunchKernelGGL((KERNEL<R, NRM, false, 16>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);                     \
   } while (0)
-#define TS_LAUNCH(KERNEL, R, b, st, a) do {                                                                              \
+#define TS_LAUNCH(KERNEL, R, b, st, ...) do {                                                                            \
     const LaunchShape L = launch_shape(b);                                                                               \
     if (sizeof(R) == 4 || L.lpe != 16) {   /* a statically known model (tsim_static.h): instantiated in its own translation unit (fp64: not four environments per wavefront) */ \
       const int km_ = kernel_mode(b);                                                                                     \
-      if (km_ == TS_KM_STATIC) { ts_static_pusher_launch(a, L.lpe, L.grid, L.lds, st); break; }                           \
-      if (km_ == TS_KM_PARAM) { ts_param_pusher_launch(a, L.lpe, L.grid, L.lds, st); break; }                             \
+      if (km_ == TS_KM_STATIC) { ts_static_pusher_launch(__VA_ARGS__, L.lpe, L.grid, L.lds, st); break; }                 \
+      if (km_ == TS_KM_PARAM) { ts_param_pusher_launch(__VA_ARGS__, L.lpe, L.grid, L.lds, st); break; }                   \
     }                                                                                                                     \
-    if (b->has_exp) hipLaunchKernelGGL((KERNEL<R, 16, true, 64>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);            \
-    else if (b->nr <= 8) TS_LAUNCH_L(KERNEL, R, 8, L, st, a);                                                            \
-    else TS_LAUNCH_L(KERNEL, R, 16, L, st, a);                                                                           \
+    if (b->has_exp) hipLaunchKernelGGL((KERNEL<R, 16, true, 64>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);  \
+    else if (b->nr <= 8) TS_LAUNCH_L(KERNEL, R, 8, L, st, __VA_ARGS__);                                                  \
+    else TS_LAUNCH_L(KERNEL, R, 16, L, st, __VA_ARGS__);                                                                 \
   } while (0)
 
 // Pads too large for the in-kernel read-out (lanes of one environment over its taxels) are read on demand by tsim_readout; for those
@@ -887,6 +897,36 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   return 0;
 }
 
+// Chunks of sub-steps per environment in the parameter pass: enough (environment, chunk) slots for about four wavefronts per SIMD at four
+// environments per wavefront, at most one chunk per sub-step.  A function of the batch alone, so that the partial-sum buffer is sized once.
+static int pg_chunks_for(const tsim_batch* b, int n) {
+  const int want = (int)std::max<long long>(1, (16LL * b->n_simd + b->B - 1) / b->B);
+  return std::max(1, std::min(n, want));
+}
+// the parameter pass of an adjoint launch (tsim_set_param_grad): k_param_grad over the sub-steps the launch just undid, then the fixed-order
+// reduction into the caller's buffer
+template <class R>
+static int launch_param_grad(tsim_batch* b, int n, int seed_stride, int frames, const int32_t* tac_slot, const void* df_dtac, hipStream_t st) {
+  const int npair = b->I[TSIM_IH_NPAIR], nsensor = b->I[TSIM_IH_NSENSOR];
+  PgArgs<R> p;
+  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = n; p.t_end = b->t_cur;
+  p.seed_stride = seed_stride; p.frames = frames; p.tac_slot = tac_slot; p.tape = (const R*)b->tape; p.z = (const R*)b->zbuf;
+  p.df_dtac = (const R*)df_dtac; p.nchunk = pg_chunks_for(b, n); p.chunk_len = (n + p.nchunk - 1) / p.nchunk;
+  p.nchunk = (n + p.chunk_len - 1) / p.chunk_len;          // (no empty chunk)
+  p.P = ts_pg_count(npair, nsensor, b->nr); p.part = (R*)b->pgpart; p.stage_cpt = b->stage_cpt;
+  if (p.nchunk > b->pg_chunks) return fail("param_grad: partial-sum buffer too small");
+  const LaunchShape L = launch_shape(b);
+  const int ns = TS_WAVE / (b->has_exp ? TS_WAVE : L.lpe);
+  const unsigned grid = (unsigned)(p.nchunk * ((b->B + ns - 1) / ns));
+  ts_param_grad_launch(p, b->has_exp != 0, b->has_exp ? TS_WAVE : L.lpe, grid, lds_bytes_for(b, ns), st);
+  HIPCHK(hipGetLastError());
+  PgReduceArgs<R> r{(const R*)b->pgpart, p.nchunk, b->B, p.P, (R*)b->dLdp, b->nfrec, npair, nsensor, b->nr,
+                    b->I[TSIM_IH_FOFF_PAIR], b->I[TSIM_IH_FOFF_SENSOR], b->I[TSIM_IH_FOFF_DOF]};
+  ts_param_reduce_launch(r, st);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 template <class R>
 static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, const int32_t* tac_slot, const void* df_dq, const void* df_dvar, const void* df_dtac, void* df_du, hipStream_t st) {
   BwdArgs<R> a;
@@ -897,10 +937,12 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
     KtScope kt_(b, TSIM_KT_BACKWARD, st);
     const int keep_ = b->lpe_forced;
     if (b->ab_bwd_lpe) b->lpe_forced = b->ab_bwd_lpe;      // A/B (TSIM_BWD_LPE at creation): another launch shape for the adjoint kernel (the tape does not depend on it)
-    TS_LAUNCH(k_backward, R, b, st, a);
+    if (b->dLdp) TS_LAUNCH(k_backward_z, R, b, st, a, (R*)b->zbuf);      // the same variant's SAVEZ twin: z of every sub-step for the parameter pass
+    else TS_LAUNCH(k_backward, R, b, st, a);
     b->lpe_forced = keep_;
   }
   HIPCHK(hipGetLastError());
+  if (b->dLdp) return launch_param_grad<R>(b, n, seed_stride, frames, tac_slot, df_dtac, st);
   return 0;
 }
 
@@ -983,6 +1025,7 @@ void tsim_batch_destroy(tsim_batch* b) {
   for (auto& k : b->kt) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
   for (hipEvent_t e : b->kt_free) (void)hipEventDestroy(e);
   (void)hipFree(b->dFenv); (void)hipFree(b->dI); (void)hipFree(b->dF); (void)hipFree(b->tape); (void)hipFree(b->lamq); (void)hipFree(b->lamv); (void)hipFree(b->evals); (void)hipFree(b->helped); (void)hipFree(b->gnorm); (void)hipFree(b->order); (void)hipFree(b->order_ep); (void)hipFree(b->prev); (void)hipFree(b->poseR); (void)hipFree(b->poseD); (void)hipFree(b->fposeR); (void)hipFree(b->fposeD); (void)hipFree(b->dKmask); (void)hipFree(b->dFlag);
+  (void)hipFree(b->zbuf); (void)hipFree(b->pgpart);
   delete b;
 }
 
@@ -1131,6 +1174,22 @@ int tsim_set_env_tables(tsim_batch* b, const void* tables, void* stream) {
   return 0;
 }
 int tsim_table_size(const tsim_batch* b) { return b->nfrec; }
+
+int tsim_set_param_grad(tsim_batch* b, void* dL_dtables) {
+  if (dL_dtables && (!b->zbuf || !b->pgpart)) {
+    TS_DEVICE(b);
+    const int chunks = pg_chunks_for(b, b->cap);
+    const size_t zb = (size_t)b->cap * b->B * b->nr * b->esz;
+    const size_t pb = (size_t)chunks * b->B * ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr) * b->esz;
+    if (hipMalloc(&b->zbuf, std::max<size_t>(zb, 8)) != hipSuccess || hipMalloc(&b->pgpart, std::max<size_t>(pb, 8)) != hipSuccess) {
+      (void)hipGetLastError(); (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); b->zbuf = nullptr; b->pgpart = nullptr;
+      return fail("set_param_grad: hipMalloc failed");
+    }
+    b->pg_chunks = chunks;
+  }
+  b->dLdp = dL_dtables;
+  return 0;
+}
 
 int tsim_reset(tsim_batch* b, const void* q0, const void* qd0, int backward_flag, void* stream) {
   if (!q0) return fail("reset: q0 is null");

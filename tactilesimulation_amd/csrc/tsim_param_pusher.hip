@@ -36,3 +36,14 @@ void ts_param_pusher_launch(const BwdArgs<double>& a, int lpe, unsigned grid, si
   if (lpe == 32) hipLaunchKernelGGL((k_backward<double, 8, false, 32, false, TsParamPusher>), dim3(grid), dim3(TS_WAVE), lds, st, a);
   else hipLaunchKernelGGL((k_backward<double, 8, false, 64, false, TsParamPusher>), dim3(grid), dim3(TS_WAVE), lds, st, a);
 }
+
+// the SAVEZ twins of the adjoint kernels above (tsim_set_param_grad): the same instantiations that also save z of every sub-step
+void ts_param_pusher_launch(const BwdArgs<float>& a, float* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st) {
+  if (lpe == 16) hipLaunchKernelGGL((k_backward_z<float, 8, false, 16, false, TsParamPusher>), dim3(grid), dim3(TS_WAVE), lds, st, a, zsave);
+  else if (lpe == 32) hipLaunchKernelGGL((k_backward_z<float, 8, false, 32, false, TsParamPusher>), dim3(grid), dim3(TS_WAVE), lds, st, a, zsave);
+  else hipLaunchKernelGGL((k_backward_z<float, 8, false, 64, false, TsParamPusher>), dim3(grid), dim3(TS_WAVE), lds, st, a, zsave);
+}
+void ts_param_pusher_launch(const BwdArgs<double>& a, double* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st) {
+  if (lpe == 32) hipLaunchKernelGGL((k_backward_z<double, 8, false, 32, false, TsParamPusher>), dim3(grid), dim3(TS_WAVE), lds, st, a, zsave);
+  else hipLaunchKernelGGL((k_backward_z<double, 8, false, 64, false, TsParamPusher>), dim3(grid), dim3(TS_WAVE), lds, st, a, zsave);
+}

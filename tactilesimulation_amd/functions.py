@@ -9,6 +9,8 @@
   forward kernel launch per env-step and one adjoint launch per env-step (tactilesimulation_amd.host.BatchSim).
 * `BatchedEpisodicSimFunction` — batched counterpart of EpisodicSimFunction: the whole open-loop episode of B
   environments in ONE forward launch and ONE adjoint launch (tsim_rollout / tsim_backward_episode).
+* `BatchedEpisodicParamSimFunction` — the same episode with the per-environment numeric tables as one more differentiable
+  input (the reference's flag_p / df_dp, batched, for contact, tactile and damping parameters: include/tsim.h tsim_set_param_grad).
 """
 import numpy as np
 import torch
@@ -182,4 +184,60 @@ class BatchedEpisodicSimFunction(autograd.Function):
         lq, lv = sim.get_adjoint()
         g = (lq.to(ctx.in_dtype) if ctx.need[0] else None, lv.to(ctx.in_dtype) if ctx.need[1] else None,
              du.to(ctx.in_dtype) if ctx.need[2] else None)
+        return g + (None, None, None, None)
+
+
+class BatchedEpisodicParamSimFunction(autograd.Function):
+    """(q0[B, ndof_r], qdot0[B, ndof_r], actions[T, B, ndof_u], tables[B, table_size], tactile_masks bool[T], batch_sim, grad_mode, num_steps=1)
+        -> qs[T, B, ndof_r], vars[T, B, ndof_var], tactiles[sum(mask), B, ndof_tactile]
+
+    BatchedEpisodicSimFunction with the environments' numeric tables (BatchSim.set_env_tables: one row per environment, the model's F[] layout)
+    as an input: forward sets them and runs the episode, backward returns next to the q0 / qdot0 / action gradients (the same numbers as
+    BatchedEpisodicSimFunction's) the gradient w.r.t. the tables.  It is non-zero only at model.param_columns() — contact pair and tactile
+    sensor kn kt mu damping, dof damping; masses, geometry and the rest of a row are not differentiated.  A shared parameter is
+    `base.expand(B, -1)`: autograd sums the rows.  The tables stay set on the batch after forward (its backward needs them)."""
+
+    @staticmethod
+    def forward(ctx, q0, qdot0, actions, tables, tactile_masks, sim, grad_mode, num_steps=1):
+        ctx.sim, ctx.T, ctx.num_steps = sim, int(actions.shape[0]), int(num_steps)
+        ctx.need = (q0.requires_grad, qdot0.requires_grad, actions.requires_grad, tables.requires_grad)
+        ctx.in_dtype, ctx.tab_dtype = actions.dtype, tables.dtype
+        ctx.tactile_masks = tactile_masks
+        ctx.tables = tables.detach().to(device=sim.device, dtype=sim.dtype).contiguous()
+        sim.set_env_tables(ctx.tables)
+        sim.reset(q0.detach(), qdot0.detach(), backward_flag=grad_mode)
+        out = sim.rollout(actions.detach(), ctx.num_steps, tactile_mask=tactile_masks)
+        qs, vars_, tacs = out["q"], out.get("var"), out.get("tactile")
+        if vars_ is None:
+            vars_ = qs.new_zeros((ctx.T, sim.B, 0))
+        if tacs is None:
+            tacs = qs.new_zeros((0, sim.B, 0))
+        ctx.status = out["status"]
+        if grad_mode:
+            sim.cache_save()
+        res = tuple(t.to(actions.dtype) for t in (qs, vars_, tacs))
+        if not grad_mode:
+            ctx.mark_non_differentiable(*res)
+        return res
+
+    @staticmethod
+    def backward(ctx, df_dq, df_dvar, df_dtactile):
+        sim = ctx.sim
+        sim.cache_pop()
+        if getattr(sim, "_env_tables", None) is not ctx.tables:      # another episode set its own tables since: the adjoint needs this one's
+            sim.set_env_tables(ctx.tables)
+        gtab = None
+        if ctx.need[3]:
+            gtab = torch.zeros_like(ctx.tables)
+            sim.set_param_grad(gtab)
+        try:
+            du = sim.backward_episode(ctx.T, ctx.num_steps, df_dq, df_dvar if sim.ndof_var else None,
+                                      df_dtactile if (sim.ndof_tactile and df_dtactile.shape[0] > 0) else None,
+                                      tactile_mask=ctx.tactile_masks)
+        finally:
+            if gtab is not None:
+                sim.set_param_grad(None)
+        lq, lv = sim.get_adjoint()
+        g = (lq.to(ctx.in_dtype) if ctx.need[0] else None, lv.to(ctx.in_dtype) if ctx.need[1] else None,
+             du.to(ctx.in_dtype) if ctx.need[2] else None, gtab.to(ctx.tab_dtype) if gtab is not None else None)
         return g + (None, None, None, None)

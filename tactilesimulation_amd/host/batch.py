@@ -92,6 +92,19 @@ class BatchSim:
         if tables is not None:
             tables = self._chk(tables, capi.lib().tsim_table_size(self._h), "tables")
         capi.check(capi.lib().tsim_set_env_tables(self._h, _ptr(tables), self._stream()))
+        self._env_tables = tables      # (the batch reads these rows in every launch: keep them alive)
+
+    def set_param_grad(self, buf):
+        """Table gradient (include/tsim.h tsim_set_param_grad): while `buf` ([B, table_size] of the batch's dtype, on its device) is set, every
+        backward_steps / backward_episode ADDS dL/d(entry) to it for the columns model.param_columns() names (contact pair and sensor kn kt mu
+        damping, dof damping) and leaves the other columns untouched.  None switches it off.  The batch keeps a reference to the buffer."""
+        if buf is not None:
+            n = capi.lib().tsim_table_size(self._h)
+            if buf.device != self.device or buf.dtype != self.dtype or tuple(buf.shape) != (self.B, n) or not buf.is_contiguous():
+                raise ValueError("set_param_grad: expected a contiguous [%d, %d] %s tensor on %s, got %s %s on %s"
+                                 % (self.B, n, self.dtype, self.device, tuple(buf.shape), buf.dtype, buf.device))
+        capi.check(capi.lib().tsim_set_param_grad(self._h, _ptr(buf)))
+        self._param_grad = buf
 
     def reset(self, q0, qd0=None, backward_flag=False):
         q0 = self._chk(q0, self.ndof_r, "q0")

@@ -274,6 +274,21 @@ class CompiledModel:
             return int(I[B.TSIM_IH_FOFF_DOF]) + (d0 + key[1]) * B.TSIM_DF_SIZE + {"damping": B.TSIM_DF_DAMPING}[field]
         raise KeyError(kind)
 
+    PARAM_FIELDS = ("kn", "kt", "mu", "damping")
+
+    def param_columns(self):
+        """[(kind, key, field, column)] of every table entry tsim_set_param_grad / BatchSim.set_param_grad computes a gradient for: per contact
+        pair and per tactile sensor kn kt mu damping, per dof its damping (key, field and column as table_offset takes / returns them).  Every
+        other column of a table gradient is left untouched by the adjoint."""
+        cols = []
+        for k in self.meta["pair_keys"]:
+            cols += [("pair", tuple(k), f, self.table_offset("pair", tuple(k), f)) for f in self.PARAM_FIELDS]
+        for s in self.meta["sensor_names"]:
+            cols += [("sensor", s, f, self.table_offset("sensor", s, f)) for f in self.PARAM_FIELDS]
+        for j, (d0, nd) in sorted(self.meta["dof_of_joint"].items(), key=lambda kv: kv[1][0]):
+            cols += [("dof", (j, k), "damping", self.table_offset("dof", (j, k), "damping")) for k in range(nd)]
+        return cols
+
     ndof_r = property(lambda s: int(s.I[B.TSIM_IH_NR]))
     ndof_u = property(lambda s: int(s.I[B.TSIM_IH_NU]))
     ndof_var = property(lambda s: 3 * int(s.I[B.TSIM_IH_NVAR]))

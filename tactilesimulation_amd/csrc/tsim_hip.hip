@@ -1389,8 +1389,9 @@ int tsim_debug_stamps(tsim_batch* b, long long* cycles) { b->bwd_stamps = cycles
 
 int tsim_debug_eval(tsim_batch* b, const void* q1, const void* q0, const void* qd0, const void* u, void* g_out, void* H_out, long long* cycles, void* stream) {
   TS_DEVICE(b);
-  // one environment per wavefront, unless TSIM_LPE forces a packed shape (nr <= 8 models: the stamped variant is NRM 8)
-  const int lpe = (b->lpe_forced && !b->has_exp && (!cycles || b->nr <= 8)) ? b->lpe_forced : TS_WAVE;
+  // one environment per wavefront, unless TSIM_LPE forces a packed shape (nr <= 8 models: the stamped variant is NRM 8) — the shape the steps
+  // take, wider where the forced one's LDS does not fit (launch_shape)
+  const int lpe = (b->lpe_forced && !b->has_exp && (!cycles || b->nr <= 8)) ? launch_shape(b).lpe : TS_WAVE;
   const int ns = TS_WAVE / lpe;
   const dim3 grid((b->B + ns - 1) / ns), blk(TS_WAVE);
   const size_t lds = lds_bytes_for(b, ns);

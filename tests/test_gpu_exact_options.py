@@ -13,6 +13,8 @@ What they skip contributes exact zeros / is never read, so a batch with both off
 law, every trial a full evaluation — must give the SAME outputs, the same evaluation counts and the same gradients (torch.equal: up to the sign
 of a zero).  (Parity of the default configuration with the oracle is what tests/test_gpu_models.py, test_gpu_configs.py and
 test_gpu_reference_pins.py assert: both options are on by default there.)"""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -25,7 +27,29 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
+# random models with general-primitive contact (tests/random_corpus.py: small corpus 9 / 86 / 64 / 93, large corpus, chain16: cuboid, sphere and
+# cylinder pairs, ndof_r 9 .. 16; the fp64 batches of the large ones do not fit two environments per wavefront and skip the 32-lane tests), started from the contact sampler's states so that the fp32 far test decides points that are really near
+RANDOM = ["random:9", "random:86", "random:64", "random:93", "random:L22", "random:L45", "random:L5", "random:chain16"]
+
+
+def _random_case(case, B):
+    import pathlib
+    import sys
+    import tempfile
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import random_corpus as RC
+    case = case if case[0] in "Lc" else int(case)
+    m, rng = RC.draw(case, pathlib.Path(tempfile.mkdtemp(prefix="tsim_ex_")))
+    states = RC.contact_states(m, RC.state_seed(case))
+    assert states and m.ndof_u >= 1, case
+    q0 = np.stack([states[e % len(states)][0] for e in range(B)]) + 0.005 * rng.normal(size=(B, m.ndof_r))
+    u = rng.uniform(-1, 1, size=(B, 6, m.ndof_u))
+    return m, q0, u, 2
+
+
 def _case(name, B):
+    if name.startswith("random:"):
+        return _random_case(name[7:], B)
     m = load_model(asset(name))
     if name == "pusher":
         q0, u, _ = push_workload(B, 10, seed=3)
@@ -57,7 +81,7 @@ def _run(m, q0, u, S, dtype, cull, trials, static, helpers=False, lanes=0, first
     g = torch.Generator().manual_seed(9)
     wq = torch.randn(T, B, m.ndof_r, generator=g, dtype=torch.float64).to(DEV, dtype)
     wv = torch.randn(T, B, m.ndof_var, generator=g, dtype=torch.float64).to(DEV, dtype) if m.ndof_var else None
-    wt = torch.randn(T, B, m.ndof_tactile, generator=g, dtype=torch.float64).to(DEV, dtype)
+    wt = torch.randn(T, B, m.ndof_tactile, generator=g, dtype=torch.float64).to(DEV, dtype) if m.ndof_tactile else None
     du = sim.backward_episode(T, S, wq, wv, wt)
     lq, lv = sim.get_adjoint()
     return ro, ev, du, lq, lv, sim.kernel_variant(), sim.last_helper_trials().copy(), sim.launch_info()["lanes_per_env"]
@@ -73,7 +97,7 @@ def _same(a, b, tag):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
-@pytest.mark.parametrize("name", ["pusher", "dclaw_position_control", "tactile_insertion"])
+@pytest.mark.parametrize("name", ["pusher", "dclaw_position_control", "tactile_insertion"] + RANDOM)
 def test_the_shortcuts_change_no_number_on_the_generic_kernels(name, dtype):
     B = 256
     m, q0, u, S = _case(name, B)
@@ -96,7 +120,7 @@ def test_the_shortcuts_change_no_number_on_the_compiled_in_kernels(pusher_model)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
-@pytest.mark.parametrize("name,lanes", [("pusher", 16), ("pusher", 32), ("dclaw_position_control", 32), ("tactile_insertion", 32)])
+@pytest.mark.parametrize("name,lanes", [("pusher", 16), ("pusher", 32), ("dclaw_position_control", 32), ("tactile_insertion", 32)] + [(r, 32) for r in RANDOM])
 def test_helper_slots_change_no_number_on_the_generic_kernels(name, lanes, dtype):
     """Finished slots evaluating another slot's next line-search trials: same iterates, flags, evaluation counts (trial points judged), taped matrices
     (the gradients come from them) as the loop without helpers, with and without the other two shortcuts — and the helper path did run."""
@@ -239,7 +263,7 @@ def test_helper_slots_change_no_number_on_the_compiled_in_kernels(pusher_model, 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("name,lanes,static", [("pusher", 16, False), ("pusher", 32, False), ("pusher", 16, True), ("pusher", 64, True), ("dclaw_position_control", 32, False),
-                                               ("tactile_insertion", 32, False), ("tactile_insertion", 64, False)])
+                                               ("tactile_insertion", 32, False), ("tactile_insertion", 64, False)] + [(r, 32, False) for r in RANDOM])
 def test_value_first_trials_change_no_number_in_forward_only_launches(name, lanes, static, dtype):
     """TSIM_OPT_VALUE_FIRST on launches that record no tape (roll-out collection): states, outputs, flags and evaluation counts of the loop
     without it — alone, and together with the other three shortcuts."""

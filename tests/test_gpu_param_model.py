@@ -211,14 +211,10 @@ def test_one_structure_static_evaluation_against_the_fp64_one(pusher_model):
     assert np.median(eHa) < 3 * np.median(eHb) + 1e-7 and np.median(ega) < 3 * np.median(egb) + 1e-7
 
 
-@pytest.mark.parametrize("seed", range(16))
-def test_structure_static_kernels_on_randomly_scaled_parameters_follow_the_oracle(pusher_model, seed):
-    """Every float record of pusher.xml's blob that is a PARAMETER or a non-trivial geometric value — masses, centres of mass, inertias, joint and
-    primitive positions, end-effector offsets, dampings, limits, motor records, primitive sizes, contact and tactile parameters, contact points and
-    taxel positions — scaled by its own random factor (frames' rotations and axes are left alone: scaled they would not be rotations): the
-    batch keeps the compiled-in STRUCTURE (`param:pusher`), and the fp64 structure-static kernels land on the oracle's trajectory and gradient."""
+def _scaled_pusher(pusher_model, seed):
+    """pusher.xml's blob with every float record that is a parameter or a non-trivial geometric value scaled by its own random factor (the test
+    below says which); (model, rng after the draw)"""
     import copy
-    from oracle.oracle import OracleSim
     rng = np.random.default_rng(400 + seed)
     m = copy.deepcopy(pusher_model)
     I, F = m.I, m.F
@@ -250,6 +246,18 @@ def test_structure_static_kernels_on_randomly_scaled_parameters_follow_the_oracl
     ncpt, ntax = int(I[BL.TSIM_IH_NCPT]), int(I[BL.TSIM_IH_NTAXEL])
     F[int(I[BL.TSIM_IH_FOFF_CPT]):int(I[BL.TSIM_IH_FOFF_CPT]) + 3 * ncpt] *= fac(3 * ncpt)
     F[int(I[BL.TSIM_IH_FOFF_TAXEL]):int(I[BL.TSIM_IH_FOFF_TAXEL]) + 3 * ntax] *= rng.uniform(0.95, 1.05, size=3 * ntax)      # (taxel positions only)
+    return m, rng
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_structure_static_kernels_on_randomly_scaled_parameters_follow_the_oracle(pusher_model, seed):
+    """Every float record of pusher.xml's blob that is a PARAMETER or a non-trivial geometric value — masses, centres of mass, inertias, joint and
+    primitive positions, end-effector offsets, dampings, limits, motor records, primitive sizes, contact and tactile parameters, contact points and
+    taxel positions — scaled by its own random factor (frames' rotations and axes are left alone: scaled they would not be rotations): the
+    batch keeps the compiled-in STRUCTURE (`param:pusher`), and the fp64 structure-static kernels land on the oracle's trajectory and gradient."""
+    from oracle.oracle import OracleSim
+    m, rng = _scaled_pusher(pusher_model, seed)
+    F = m.F
     F[BL.TSIM_FH_TOL] = 1e-12
     B, T, S = 16, 6, 5
     q0, u, _ = push_workload(B, T, seed=60 + seed)
@@ -277,3 +285,43 @@ def test_structure_static_kernels_on_randomly_scaled_parameters_follow_the_oracl
             assert np.abs(outs[t]["tactile"][e].cpu().numpy() - tac).max() < 1e-8 * (1.0 + np.abs(tac).max())
         g = o.backward_steps(n, df_dq=np.concatenate([np.zeros((n - 1) * 7), wq[e]]), df_dtac=np.concatenate([np.zeros((n - 1) * 390), wt[e]]))
         assert np.abs(du[e].reshape(n, 6) - g).max() < 1e-7 * (1.0 + np.abs(g).max()), (seed, e, np.abs(du[e].reshape(n, 6) - g).max(), np.abs(g).max())
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_structure_static_fp32_kernels_on_randomly_scaled_parameters_follow_the_oracle(pusher_model, seed):
+    """The fp32 leg of the test above: the same 16 scalings on `param:pusher` in single precision at the XML's own Newton tolerance, against the
+    oracle at that tolerance — state and tactile frame to the fp32 bounds of tests/test_gpu_parity.py test_forward_rollout (2e-5; 2e-3 of the frame's
+    scale), dL/du to 1e-4 of its scale on every environment whose branch signature is the oracle's."""
+    from oracle.oracle import OracleSim
+    m, rng = _scaled_pusher(pusher_model, seed)
+    B, T, S = 16, 6, 5
+    q0, u, _ = push_workload(B, T, seed=60 + seed)
+    dt = torch.float32
+    sim = BatchSim(m, B, dtype=dt, tape_capacity=T * S)
+    assert sim.kernel_variant() == "param:pusher"
+    sim.reset(torch.tensor(q0, device=DEV, dtype=dt), None, backward_flag=True)
+    outs = [sim.step(torch.tensor(u[:, t], device=DEV, dtype=dt), S) for t in range(T)]
+    sig = sim.branch_signature().cpu().numpy()
+    wq = rng.normal(size=(B, 7))
+    wt = rng.normal(size=(B, 390))
+    du = sim.backward_steps(T * S, df_dq=torch.tensor(wq, device=DEV, dtype=dt), df_dtactile=torch.tensor(wt, device=DEV, dtype=dt)).double().cpu().numpy()
+    o = OracleSim(m)
+    n = T * S
+    same = 0
+    for e in range(B):
+        o.reset(q0[e], record=True)
+        so = np.zeros((n, 2), dtype=np.int64)
+        for t in range(T):
+            bad, so[t * S:(t + 1) * S] = o.forward_sig(u[e, t], S)
+            assert bad == 0 and int(outs[t]["status"][e]) == 0, (seed, e, t)
+            q, _ = o.state()
+            var, tac = o.outputs()
+            assert np.abs(outs[t]["q"][e].double().cpu().numpy() - q).max() <= 2e-5, (seed, e, t)
+            assert np.abs(outs[t]["var"][e].double().cpu().numpy() - var).max() <= 2e-4, (seed, e, t)
+            assert np.abs(outs[t]["tactile"][e].double().cpu().numpy() - tac).max() <= 2e-3 * max(np.abs(tac).max(), 1e-4), (seed, e, t)
+        if not np.array_equal(so, sig[:, e]):
+            continue      # (a kink crossed on different sides: the gradients of two smooth pieces)
+        same += 1
+        g = o.backward_steps(n, df_dq=np.concatenate([np.zeros((n - 1) * 7), wq[e]]), df_dtac=np.concatenate([np.zeros((n - 1) * 390), wt[e]]))
+        assert np.abs(du[e].reshape(n, 6) - g).max() <= 1e-4 * np.abs(g).max(), (seed, e, np.abs(du[e].reshape(n, 6) - g).max(), np.abs(g).max())
+    assert same >= B // 2, (seed, same)

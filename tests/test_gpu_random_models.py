@@ -15,33 +15,29 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tactilesimulation_amd", "compat"))      # `import redmax_py`
-from test_native_model_loader import _random_model      # noqa: E402
+import random_corpus as RC      # noqa: E402
+from random_corpus import N_MODELS, SEED0      # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-N_MODELS, B_, T, S = int(os.environ.get("TSIM_RANDOM_MODELS", "120")), 3, 3, 2      # (a soak: TSIM_RANDOM_MODELS=2000 TSIM_RANDOM_SEED0=100000)
-SEED0 = int(os.environ.get("TSIM_RANDOM_SEED0", "1000"))
+B_, T, S = 3, 3, 2
+LARGE = RC.LARGE + ["chain16"]      # ndof_r 13 .. 16 (tests/random_corpus.py)
 
 
-def _case(seed, tmp_path, files=False):
-    from tactilesimulation_amd.model.compiler import parse_xml, compile_spec
-    rng = np.random.default_rng(seed)
-    p = str(tmp_path / ("m%d.xml" % seed))
-    for _ in range(20):      # (the kernels take ndof_r, ndof_u <= 16 and one rotation-vector joint per model: include/tsim.h)
-        open(p, "w").write(_random_model(rng, max_dof=12, files_dir=str(tmp_path) if files else None))
-        spec = parse_xml(p)
-        m = compile_spec(spec)
-        if 1 <= m.ndof_r <= 16 and m.ndof_u <= 16 and sum(J["type"] == "free3d-exp" for J in spec["joints"]) <= 1:
-            return m, rng
-    pytest.skip("no model within the kernels' sizes")
+def _case(case, tmp_path, files=False):
+    """(model, rng) of a corpus case: an int of the small corpus (seed SEED0 + case), a large-corpus id or "chain16" (tests/random_corpus.py)"""
+    r = RC.draw(case, tmp_path, files)
+    if r is None:
+        pytest.skip("no model within the kernels' sizes")
+    return r
 
 
 @pytest.mark.parametrize("lanes,dtype,files", [(0, torch.float64, False), (32, torch.float64, False), (16, torch.float64, False), (0, torch.float64, True), (32, torch.float64, True)])
-@pytest.mark.parametrize("seed", range(N_MODELS))
+@pytest.mark.parametrize("seed", list(range(N_MODELS)) + LARGE)
 def test_random_model_follows_the_oracle(seed, lanes, dtype, files, tmp_path):
     """files: abstract bodies with contact-point files as general bodies, abstract taxel files as sensors (the D'Claw vocabulary)"""
     from oracle.oracle import OracleSim
     from tactilesimulation_amd.host.batch import BatchSim
-    m, rng = _case(SEED0 + seed, tmp_path, files)
+    m, rng = _case(seed, tmp_path, files)
     nr, nu, nv, nt = m.ndof_r, m.ndof_u, m.ndof_var, m.ndof_tactile
     q0 = 0.02 * rng.normal(size=(B_, nr))
     u = rng.uniform(-1, 1, size=(B_, T, max(nu, 1)))[:, :, :nu]
@@ -51,7 +47,7 @@ def test_random_model_follows_the_oracle(seed, lanes, dtype, files, tmp_path):
     tq, tg = (2e-4, 2e-3) if f32 else (1e-8, 1e-7)      # state / gradient tolerance relative to the scale of the quantity (fp32: the BASELINE 1e-4 with a margin for models nobody tuned)
     sim = BatchSim(m, B_, dtype=dt, tape_capacity=T * S)
     if lanes:      # two / four environments per wavefront where the model's LDS footprint allows it (the library falls back otherwise)
-        sim.set_lanes_per_env(lanes)
+        RC.force_lanes(sim, m, lanes)
     sim.reset(torch.tensor(q0, device=dev, dtype=dt), None, backward_flag=True)
     outs = [sim.step(torch.tensor(u[:, t], device=dev, dtype=dt).reshape(B_, nu), S, want_qd=True) for t in range(T)]
     if nv or nt:      # the on-demand read-out (tsim_readout: k_readout + k_taxels) of the final state == what the last step returned, bit for bit
@@ -110,13 +106,13 @@ def test_random_model_follows_the_oracle(seed, lanes, dtype, files, tmp_path):
 
 
 @pytest.mark.parametrize("lanes,dtype", [(0, torch.float64), (32, torch.float64), (16, torch.float32), (32, torch.float32)])
-@pytest.mark.parametrize("seed", range(0, N_MODELS, 3))
+@pytest.mark.parametrize("seed", list(range(0, N_MODELS, 3)) + LARGE)
 def test_episode_launches_equal_the_step_loop_on_random_models(seed, lanes, dtype, tmp_path):
     """tsim_rollout + tsim_backward_episode (one launch each way per episode: free-running slots, helper slots, LPT order, deferred read-out)
     against T x tsim_step + tsim_backward_steps on the same random models — bit for bit, both precisions, ragged batch (11 environments, so that
     wavefronts carry 1 - 4 of them and the last one is partly empty), a tactile mask, per-frame seeds."""
     from tactilesimulation_amd.host.batch import BatchSim
-    m, rng = _case(SEED0 + seed, tmp_path)
+    m, rng = _case(seed, tmp_path)
     nr, nu, nv, nt = m.ndof_r, m.ndof_u, m.ndof_var, m.ndof_tactile
     B2, T2, S2 = 11, 4, 3
     dev = "cuda:0"
@@ -129,7 +125,7 @@ def test_episode_launches_equal_the_step_loop_on_random_models(seed, lanes, dtyp
     a, b = (BatchSim(m, B2, dtype=dtype, tape_capacity=T2 * S2) for _ in range(2))
     for sim in (a, b):
         if lanes:
-            sim.set_lanes_per_env(lanes)
+            RC.force_lanes(sim, m, lanes)
         sim.reset(q0, None, backward_flag=True)
     ro = a.rollout(u, S2, want_qd=True, tactile_mask=mask)
     steps = [b.step(u[t], S2, want_qd=True) for t in range(T2)]
@@ -172,7 +168,7 @@ def test_per_environment_tables_equal_separately_edited_models_on_random_models(
     import copy
     import tactilesimulation_amd.model.blob as BL
     from tactilesimulation_amd.host.batch import BatchSim
-    m, rng = _case(SEED0 + seed, tmp_path)
+    m, rng = _case(seed, tmp_path)
     nr, nu, nv, nt = m.ndof_r, m.ndof_u, m.ndof_var, m.ndof_tactile
     Bt, Tt, St = 5, 3, 2
     dev, dt = "cuda:0", torch.float64
@@ -241,7 +237,7 @@ def test_reference_call_sequence_on_random_model_files(seed, tmp_path):
     import redmax_py as redmax
     from oracle.oracle import OracleSim
     from tactilesimulation_amd.functions import StepSimFunction
-    m, rng = _case(SEED0 + seed, tmp_path, files=True)
+    m, rng = _case(seed, tmp_path, files=True)
     nr, nu, nv, nt = m.ndof_r, m.ndof_u, m.ndof_var, m.ndof_tactile
     if nu == 0:
         pytest.skip("no motor in this model")
@@ -289,7 +285,7 @@ def test_fp32_kernels_on_the_random_models_in_distribution(tmp_path):
     dq, dtac, one_sided, total = [], [], 0, 0
     for seed in range(N_MODELS):
         try:
-            m, rng = _case(SEED0 + seed, tmp_path)
+            m, rng = _case(seed, tmp_path)
         except BaseException:      # (pytest.skip inside _case)
             continue
         m.F[BL.TSIM_FH_TOL] = 1e-5
@@ -318,3 +314,143 @@ def test_fp32_kernels_on_the_random_models_in_distribution(tmp_path):
     assert len(dq) >= 950 and one_sided <= 0.02 * total, (len(dq), one_sided, total)
     assert np.quantile(dq, 0.5) < 1e-6 and np.quantile(dq, 0.9) < 1e-5 and np.quantile(dq, 0.99) < 1e-3 and (dq > 1e-2).mean() <= 2e-3, [float(np.quantile(dq, x)) for x in (0.5, 0.9, 0.99, 1.0)]
     assert len(dtac) > 100 and np.quantile(dtac, 0.99) < 1e-4 and dtac.max() < 1e-2, [float(np.quantile(dtac, x)) for x in (0.5, 0.99, 1.0)]
+
+
+# minimum numbers of compared contact states per coverage key (tests/random_corpus.py state_keys) whose contact part of H is far above the tolerance:
+# about 3/4 of what the seeded sampler finds on both corpora and chain16 (537 states; profiles/r08_fp32_random_models.md)
+GH_MIN = {("prim", "plane"): 350, ("prim", "cuboid"): 16, ("prim", "sphere"): 38, ("prim", "cylinder"): 24, ("sphere_plane",): 180,
+          ("stick", "plane"): 340, ("slip", "plane"): 70, ("stick", "cuboid"): 14, ("slip", "cuboid"): 8, ("stick", "sphere"): 30,
+          ("slip", "sphere"): 18, ("stick", "cylinder"): 20, ("slip", "cylinder"): 8}
+STATS = os.environ.get("TSIM_RM_STATS")      # a directory: the error distributions of the fp32 tests below are written there as JSON (profiles/)
+
+
+def _stats(name, d):
+    if STATS:
+        import json
+        with open(os.path.join(STATS, name + ".json"), "w") as f:
+            json.dump(d, f)
+
+
+def _q(x):
+    x = np.asarray(x)
+    return [float(np.quantile(x, p)) for p in (0.5, 0.9, 0.99, 1.0)] if len(x) else []
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-3), (torch.float64, 1e-9)])
+def test_residual_and_newton_matrix_on_random_structures(dtype, tol, tmp_path):
+    """g and H = dg/dq1 of one evaluation (tsim_debug_eval) on the generic kernels against the oracle's dual-number Jacobian, on every model of both
+    corpora and chain16, at contact states of a seeded rejection sampler (random_corpus.contact_states), at 64 / 32 / 16 lanes per environment, pair
+    cull on and off.  fp32 builds the contact part of H with its own accumulated 6 x 12 matrix (pair_contacts_matrix) and culls points with an fp32
+    distance first: a Newton matrix that is wrong there still converges to the same root, so only this comparison sees it.  H per ROW, relative to
+    that row's largest oracle entry (a stiff contact row cannot hide an error in another); the bound of tests/test_gpu_parity.py's pusher states.
+    Non-vacuity: the contact part of the oracle's H (H minus H of the model with kn = kt = 0 on the touching pairs) is above 10 x the tolerance in
+    the states counted per primitive type and friction branch."""
+    from oracle.oracle import OracleSim
+    from tactilesimulation_amd.host.batch import BatchSim
+    dev = "cuda:0"
+    counts = {k: 0 for k in GH_MIN}
+    eg, eh, nstates, shapes = [], [], 0, set()
+    for case in list(range(N_MODELS)) + LARGE:
+        r = RC.draw(case, tmp_path)
+        if r is None or not RC.pair_info(r[0]):
+            continue
+        m = r[0]
+        states = RC.contact_states(m, RC.state_seed(case))
+        if not states:
+            continue
+        o = OracleSim(m)
+        ref = []
+        for q1, q0, qd0, u, c in states:
+            go, Ho = o.residual(q1, q0, qd0, u, which=0)
+            _, H0 = OracleSim(RC.without_contact(m, {p for p, *_ in c})).residual(q1, q0, qd0, u, which=0)
+            ref.append((go, Ho))
+            if (np.abs(Ho - H0).max(1) / np.abs(Ho).max(1)).max() > 10 * tol:
+                for k in RC.state_keys(m, c):
+                    if k in counts:
+                        counts[k] += 1
+        nstates += len(states)
+        B = len(states)
+        sim = BatchSim(m, B, dtype=dtype, tape_capacity=1)
+        assert sim.kernel_variant() == "generic"
+        args = [torch.tensor(np.stack([s_[j] for s_ in states]).reshape(B, d), device=dev, dtype=dtype) for j, d in enumerate([m.ndof_r] * 3 + [m.ndof_u])]
+        for lanes in (64, 32, 16):
+            got = RC.force_lanes(sim, m, lanes)
+            shapes.add((m.ndof_r, lanes, got))
+            for cull in (False, True):
+                sim.set_option(BatchSim.OPT_PAIR_CULL, cull)
+                g, H = sim.debug_eval(*args)
+                g, H = g.double().cpu().numpy(), H.double().cpu().numpy()
+                for e, (go, Ho) in enumerate(ref):
+                    # g relative to the larger of itself and the size of its inertial / stiffness part H (q1 - q0): at a random state g can be a small
+                    # difference of large terms, whose rounding is relative to the terms
+                    rg = np.abs(g[e] - go).max() / max(np.abs(go).max(), np.abs(Ho @ (states[e][0] - states[e][1])).max(), 1e-6)
+                    rh = (np.abs(H[e] - Ho).max(1) / np.abs(Ho).max(1)).max()
+                    eg.append(rg)
+                    eh.append(rh)
+                    assert np.isfinite(rg) and np.isfinite(rh) and rg <= tol and rh <= tol, (case, lanes, got, cull, e, rg, rh, m.ndof_r)
+    _stats("gh_%s" % str(dtype)[-7:], {"states": nstates, "counts": {"/".join(k): v for k, v in counts.items()}, "g": _q(eg), "H_row": _q(eh),
+                                        "shapes": sorted(shapes)})
+    assert nstates >= 450, nstates
+    assert all(counts[k] >= GH_MIN[k] for k in GH_MIN), {"/".join(k): (counts[k], GH_MIN[k]) for k in GH_MIN}
+
+
+def test_fp32_adjoint_on_the_random_models_in_distribution(tmp_path):
+    """The fp32 generic kernels' adjoint — dL/du of every sub-step, dL/dq0, dL/dqdot0 — against the fp64 oracle on both corpora and chain16, 8
+    environments per model, the kernels at `tol` 1e-5 (see the test above), the oracle at the same `tol` and max_iter >= 100 — the same Newton loop,
+    so that what is measured is the kernels' arithmetic: against an oracle at `tol` 1e-12 the distribution is that of the 1e-5 root itself, and the
+    fp64 kernels at `tol` 1e-5 show the same one (median 1e-5, 99 % 8e-3, max 5e-2; profiles/r08_fp32_random_models.md).
+    Compared: environments whose branch signature of every sub-step (tsim_debug_signature) is the oracle's (forward_sig) and that both sides
+    converged — a gradient across a contact / friction kink is not comparable.  Per environment and quantity, relative to the quantity's largest
+    oracle entry.  >= 300 environments; >= 99 % within 1e-4; none above 1e-2 (an environment on the oracle's branches with a wrong gradient is a bug)."""
+    import tactilesimulation_amd.model.blob as BL
+    from oracle.oracle import OracleSim
+    from tactilesimulation_amd.host.batch import BatchSim
+    B8, T8, S8 = 8, 3, 2
+    n = T8 * S8
+    dev, dt = "cuda:0", torch.float32
+    errs, worst, excluded = [], [], 0
+    for case in list(range(N_MODELS)) + LARGE:
+        r = RC.draw(case, tmp_path)
+        if r is None:
+            continue
+        m, rng = r
+        m.F[BL.TSIM_FH_TOL] = 1e-5
+        m.I[BL.TSIM_IH_MAX_ITER] = max(int(m.I[BL.TSIM_IH_MAX_ITER]), 100)
+        nr, nu, nv, nt = m.ndof_r, m.ndof_u, m.ndof_var, m.ndof_tactile
+        q0 = 0.02 * rng.normal(size=(B8, nr))
+        u = rng.uniform(-1, 1, size=(B8, T8, max(nu, 1)))[:, :, :nu]
+        wq, wv, wt = rng.normal(size=(B8, nr)), rng.normal(size=(B8, nv)), rng.normal(size=(B8, nt))
+        sim = BatchSim(m, B8, dtype=dt, tape_capacity=n)
+        sim.reset(torch.tensor(q0, device=dev, dtype=dt), None, backward_flag=True)
+        st = np.stack([sim.step(torch.tensor(u[:, t], device=dev, dtype=dt).reshape(B8, nu), S8)["status"].cpu().numpy() for t in range(T8)])
+        sig = sim.branch_signature().cpu().numpy()
+        kw = {"df_dq": torch.tensor(wq, device=dev, dtype=dt)}
+        if nv:
+            kw["df_dvar"] = torch.tensor(wv, device=dev, dtype=dt)
+        if nt:
+            kw["df_dtactile"] = torch.tensor(wt, device=dev, dtype=dt)
+        du = sim.backward_steps(n, **kw).double().cpu().numpy().reshape(B8, n, nu)
+        lam_q, lam_v = (x.double().cpu().numpy() for x in sim.get_adjoint())
+        o = OracleSim(m)
+        for e in range(B8):
+            o.reset(q0[e], record=True)
+            so, bad = np.zeros((n, 2), dtype=np.int64), 0
+            for t in range(T8):
+                b_, so[t * S8:(t + 1) * S8] = o.forward_sig(u[e, t], S8)
+                bad |= b_ != 0
+            if bad or (st[:, e] != 0).any() or not np.array_equal(so, sig[:, e]):
+                excluded += 1
+                continue
+            z = lambda w, d: np.concatenate([np.zeros((n - 1) * d), w]) if d else None
+            g = o.backward_steps(n, df_dq=z(wq[e], nr), df_dvar=z(wv[e], nv) if nv else None, df_dtac=z(wt[e], nt) if nt else None)
+            aq, av = o.adjoint()
+            pairs = [(du[e], g)] if nu else []
+            pairs += [(lam_q[e], aq), (lam_v[e], av)]
+            top = max(np.abs(y).max() for _, y in pairs)
+            err = max(np.abs(x - y).max() / max(np.abs(y).max(), 1e-6 * top, 1e-30) for x, y in pairs)
+            errs.append(err)
+            worst.append((err, str(case), e))
+    errs = np.array(errs)
+    worst.sort(reverse=True)
+    _stats("adjoint_fp32", {"compared": len(errs), "excluded": excluded, "quantiles": _q(errs), "worst": worst[:10]})
+    assert len(errs) >= 300 and np.mean(errs <= 1e-4) >= 0.99 and errs.max() <= 1e-2, (len(errs), excluded, _q(errs), worst[:5])

@@ -2,7 +2,8 @@
 every joint and primitive body kind, random frames, contacts, motors, sensors, BDF1 / BDF2), by central differences.  The oracle is this
 repository's restatement of a simulator whose source is absent; what can be pinned without it is that the restatement is
 self-consistent wherever it is exercised: the fixed-model finite-difference tests (tests/test_oracle_physics.py) cover the structures of the
-reference's assets, this covers the ones they do not.  No GPU."""
+reference's assets, this covers the ones they do not — up to the largest size the HIP path takes (ndof_r = ndof_u = 16: models of the large corpus
+of tests/random_corpus.py and tests/models/chain16.xml).  No GPU."""
 import os
 import sys
 
@@ -11,8 +12,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_native_model_loader import _random_model      # noqa: E402
+import random_corpus as RC      # noqa: E402
 
 N = 60
+LARGE_FD = ["L26", "L94", "L7", "L45", "L16", "L77", "L3", "L5", "chain16"]      # ndof_r 13, 13, 14, 14, 15, 15, 16, 16, 16 (every one actuated)
 T, S = 2, 2
 
 
@@ -26,20 +29,45 @@ def _loss(o, q0, u, wq, wv, wt, record=False):
     return float(wq @ q + (wv @ var if len(wv) else 0.0) + (wt @ tac if len(wt) else 0.0))
 
 
-@pytest.mark.parametrize("seed", range(N))
+def test_the_large_corpus_covers_the_sizes_up_to_16():
+    """The GPU tests that take the large corpus cannot skip their way to green: every ndof_r of 13..16 is in it, most of it at 16, and chain16 drives
+    all 16 degrees of freedom."""
+    import collections
+    import pathlib
+    import tempfile
+    hist, nus = collections.Counter(), []
+    with tempfile.TemporaryDirectory() as d:
+        for case in RC.LARGE + ["chain16"]:
+            r = RC.draw(case, pathlib.Path(d))
+            assert r is not None, case
+            hist[r[0].ndof_r] += 1
+            nus.append(r[0].ndof_u)
+            if case == "chain16":
+                assert (r[0].ndof_r, r[0].ndof_u) == (16, 16)
+                prims = [p for p, _, _ in RC.pair_info(r[0])]
+                assert RC.PRIM_NAMES[0] in [RC.PRIM_NAMES[p] for p in prims] and any(p != 0 for p in prims)      # ground and a general-primitive pair
+    assert set(hist) == {13, 14, 15, 16} and all(hist[n] >= 3 for n in (13, 14, 15)) and hist[16] >= 8, sorted(hist.items())
+    assert len(RC.LARGE) == 24 and max(nus) == 16 and sum(n > 12 for n in nus) >= 3, nus
+
+
+@pytest.mark.parametrize("seed", list(range(N)) + LARGE_FD)
 def test_oracle_adjoint_is_the_derivative_of_its_forward_pass(seed, tmp_path):
     from oracle.oracle import OracleSim
     from tactilesimulation_amd.model.compiler import parse_xml, compile_spec
     import tactilesimulation_amd.model.blob as BL
-    rng = np.random.default_rng(5000 + seed)
-    p = str(tmp_path / "m.xml")
-    for _ in range(30):
-        open(p, "w").write(_random_model(rng, max_dof=10))
-        m = compile_spec(parse_xml(p))
-        if m.ndof_u >= 1:
-            break
+    if isinstance(seed, str):      # the large corpus and chain16
+        m, rng = RC.draw(seed, tmp_path)
+        assert m.ndof_u >= 1 and m.ndof_r >= 13
     else:
-        pytest.skip("no actuated model drawn")
+        rng = np.random.default_rng(5000 + seed)
+        p = str(tmp_path / "m.xml")
+        for _ in range(30):
+            open(p, "w").write(_random_model(rng, max_dof=10))
+            m = compile_spec(parse_xml(p))
+            if m.ndof_u >= 1:
+                break
+        else:
+            pytest.skip("no actuated model drawn")
     m.F[BL.TSIM_FH_TOL] = 1e-12                    # (roots tight enough for differences of 1e-6)
     m.I[BL.TSIM_IH_MAX_ITER] = 200
     nr, nu, nv, nt = m.ndof_r, m.ndof_u, m.ndof_var, m.ndof_tactile

@@ -346,8 +346,8 @@ template <int LPE, int N, class R> __device__ __forceinline__ void seg_sum_many(
 #pragma unroll
   for (int i = 0; i < N; ++i) v[i] = lane_bcast(v[i], 63);
 }
-// sum over lanes 0..7 of each 8-lane half of a 16-lane row (three DPP steps): for per-pair sums whose points all sit in the first 8 lanes of
-// the slot (the other lanes hold zeros), result in lanes 0..7
+// sum over each 8-lane half of a 16-lane row (three DPP steps), result in every lane of the half: for per-pair sums whose points all sit in
+// the first 8 lanes of the slot (the other lanes hold zeros, or — the fused static evaluation — the same points again)
 template <class R> __device__ __forceinline__ R half_row_sum(R x) {
   x += dpp_r<0xB1, 0xf>(x);    // quad_perm [1,0,3,2]
   x += dpp_r<0x4E, 0xf>(x);    // quad_perm [2,3,0,1]

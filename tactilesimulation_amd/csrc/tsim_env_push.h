@@ -152,11 +152,11 @@ static int push_closed_check(const tsim_batch* b, const tsim_push_policy* pol, i
   if (pol->obs_mean && b->record) return fail(std::string(who) + ": observation normalisation is for roll-out collection (reset with backward_flag = False); the adjoint launch does not undo it");
   return 0;
 }
-#define TS_LAUNCH_POLICY(KERNEL, R, b, st, a) do {                                                                                   \
+#define TS_LAUNCH_POLICY(KERNEL, R, b, km, st, a) do {                                                                               \
     const LaunchShape L = launch_shape(b);                                                                                           \
     if constexpr (sizeof(R) == 4) {      /* the statically specialised TactilePush instantiation (tsim_static_pusher.hip) */           \
-      if (kernel_mode(b) == TS_KM_STATIC && L.lpe == 16) { ts_static_pusher_launch_policy(a, L.grid, L.lds, st); break; }               \
-      if (kernel_mode(b) == TS_KM_PARAM && L.lpe == 16) { ts_param_pusher_launch_policy(a, L.grid, L.lds, st); break; }                 \
+      if ((km) == TS_KM_STATIC && L.lpe == 16) { ts_static_pusher_launch_policy(a, L.grid, L.lds, st); break; }                         \
+      if ((km) == TS_KM_PARAM && L.lpe == 16) { ts_param_pusher_launch_policy(a, L.grid, L.lds, st); break; }                           \
     }                                                                                                                                 \
     if (L.lpe == 64) hipLaunchKernelGGL((KERNEL<R, 8, false, 64, true>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);                  \
     else if (L.lpe == 32) hipLaunchKernelGGL((KERNEL<R, 8, false, 32, true>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);             \
@@ -177,7 +177,10 @@ static int push_closed_rollout_t(tsim_batch* b, const tsim_push_policy* pol, con
   a.pol = make_push_policy<R>(pol);
   a.pol.goal = (const R*)goal; a.pol.dist = (const R*)dist; a.pol.tac0 = (const R*)tac0;
   a.pol.u_out = (R*)u_out; a.pol.gl_out = (R*)gl_out; a.pol.h1_out = (R*)h1_out; a.pol.h2_out = (R*)h2_out;
-  TS_LAUNCH_POLICY(k_forward, R, b, st, a);
+  a.tk = b->tape_k;
+  const int km = kernel_mode(b);
+  if (b->record && !launches_fused(b, km, sizeof(R), true)) b->tape_k_ok = 0;      // records without K from here on
+  TS_LAUNCH_POLICY(k_forward, R, b, km, st, a);
   HIPCHK(hipGetLastError());
   b->order_valid = 0; pose_invalidate(b, st);
   return 0;
@@ -212,7 +215,8 @@ static int push_closed_backward_t(tsim_batch* b, const tsim_push_policy* pol, co
   a.pol.goal = (const R*)goal; a.pol.du_direct = (const R*)du_direct;
   a.pol.u_out = (R*)u_out; a.pol.h1_out = (R*)h1_out; a.pol.h2_out = (R*)h2_out;
   a.pol.g1_out = (R*)g1_out; a.pol.g2_out = (R*)g2_out; a.pol.g3_out = (R*)g3_out; a.pol.dobs_tac = (R*)dobs_tac;
-  TS_LAUNCH_POLICY(k_backward, R, b, st, a);
+  a.tk = b->tape_k;
+  TS_LAUNCH_POLICY(k_backward, R, b, b->tape_k_ok ? kernel_mode(b) : TS_KM_GENERIC, st, a);      // the fused adjoint reads K from the tape (launch_backward)
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -744,7 +744,7 @@ __device__ __forceinline__ void evaluate(const Ctx<R>& c, int lane, R sq, R sv, 
   TS_SYNC();
   TS_STAMP(c);
   if constexpr (ts_static_fused<MS, R>()) {
-    evaluate_static_fused<R, NRM, LPE, MS, false>(c, lane, sq, sv, sa, tang);      // a statically known model: one register-resident pass (tsim_static_eval.h)
+    evaluate_static_fused<R, NRM, LPE, MS>(c, lane, sq, sv, sa, tang);        // a statically known model: one register-resident pass (tsim_static_eval.h)
     TS_STAMP(c);
     return;
   }

@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(1024) k_order_by_evals(const int* evals, int* 
 //               the penalty law, 12 B out (the 9 axis constants only where a force acts).  ~40 registers instead of the 178 the
 //               kinematics need, so 8+ wavefronts per SIMD cover the L2 latency of the constants: this is the one kernel of the path
 //               whose time is memory traffic (RollingBall: 40 000 taxels, 480 KB per environment and read-out).
-template <class R> struct ReadArgs { const int* I; const R* F; const R* Fenv; int fstride; int B, t0; const R* tape; R* var_out; R* poseR; double* poseD; int nspt; int stage_cpt; };
+template <class R> struct ReadArgs { const int* I; const R* F; const R* Fenv; int fstride; int B, t0; const R* tape; R* var_out; R* poseR; double* poseD; int nspt; int stage_cpt; int tk; };
 
 template <class R>
 __global__ void __launch_bounds__(TS_WAVE) k_readout(ReadArgs<R> a) {
@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(TS_WAVE) k_readout(ReadArgs<R> a) {
   R* lds = reinterpret_cast<R*>(smem_raw);
   const int env = blockIdx.x, lane = threadIdx.x;
   Ctx<R> c; ctx_init(c, a.I, a.F, lds, 1, 0, lane, TS_WAVE, a.stage_cpt != 0, a.Fenv ? a.Fenv + (size_t)blockIdx.x * a.fstride : nullptr);
-  const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R));
+  const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R), a.tk);
   init_world(c, lane, TS_WAVE);
   const R* st = a.tape + ((size_t)a.t0 * a.B + env) * REC;
   if (lane < nr) { c.qD[lane] = rec_q(st)[lane]; c.q[lane] = (R)c.qD[lane]; c.qd[lane] = st[rec_qd<R>(nr) + lane]; c.qa[lane] = R(0); }
@@ -319,7 +319,7 @@ __global__ void __launch_bounds__(256) k_taxels_small(TaxArgs<R> a, int nrec) {
 // recomputed from the taped state (q as double, qd) exactly as the backward kernel re-evaluates it.  Two trajectories with
 // equal signatures went through the same smooth pieces, so their gradients are comparable; where they differ, one of them
 // crossed a contact / friction kink.  One environment per 64-lane block; lanes = points.
-template <class R> struct SigArgs { const int* I; const R* F; const R* Fenv; int fstride; int B, t_first, n; const R* tape; unsigned* out; int stage_cpt; };
+template <class R> struct SigArgs { const int* I; const R* F; const R* Fenv; int fstride; int B, t_first, n; const R* tape; unsigned* out; int stage_cpt; int tk; };
 
 __device__ __forceinline__ unsigned wave_sum_u32(unsigned x) {
   for (int off = 32; off > 0; off >>= 1) x += (unsigned)lane_gather((int)x, (int)threadIdx.x ^ off);
@@ -332,7 +332,7 @@ __global__ void __launch_bounds__(TS_WAVE) k_signature(SigArgs<R> a) {
   R* lds = reinterpret_cast<R*>(smem_raw);
   const int env = blockIdx.x, lane = threadIdx.x;
   Ctx<R> c; ctx_init(c, a.I, a.F, lds, 1, 0, lane, TS_WAVE, a.stage_cpt != 0, a.Fenv ? a.Fenv + (size_t)blockIdx.x * a.fstride : nullptr);
-  const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R));
+  const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R), a.tk);
   init_world(c, lane, TS_WAVE);
   for (int j = 0; j < a.n; ++j) {
     const R* st = a.tape + ((size_t)(a.t_first + 1 + j) * a.B + env) * REC;
@@ -407,12 +407,15 @@ struct DeviceGuard {
 };
 #define TS_DEVICE(b) DeviceGuard guard_((b)->device); if (!guard_.ok) return fail("hipSetDevice(" + std::to_string((b)->device) + ") failed")
 
-struct CacheEntry { void* buf; int len; int record; };
+struct CacheEntry { void* buf; int len; int record, tape_k_ok; };
 struct KtPair { hipEvent_t a, b; int kind; };
 struct tsim_batch {
   int B, dtype, device, cap;
   std::vector<int32_t> I; std::vector<double> F;
   int nl, nr, nu, nvar, ntax, rec;
+  // The tape records of a batch created with a compiled-in model (kernel_mode: the fused static instantiations) hold K next to H (ts_rec: tape_k).
+  // tape_k_ok: every record since the last reset was written by such an instantiation, which the fused adjoint kernels need (launch_backward)
+  int tape_k = 0, tape_k_ok = 0;
   int* dI; void* dF;             // model on device (dF in the batch's real type)
   void* dFenv; int nfrec;        // optional per-environment float tables [B][nfrec] (domain randomisation)
   void* tape;                    // [(cap+1)][B][rec]
@@ -787,10 +790,10 @@ void ts_param_pusher_launch(const BwdArgs<double>& a, double* zsave, int lpe, un
     else if (L.lpe == 32) hipLaunchKernelGGL((KERNEL<R, NRM, false, 32>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);    \
     else hipLaunchKernelGGL((KERNEL<R, NRM, false, 16>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);                     \
   } while (0)
-#define TS_LAUNCH(KERNEL, R, b, st, ...) do {                                                                            \
+#define TS_LAUNCH(KERNEL, R, b, km, st, ...) do {                                                                        \
     const LaunchShape L = launch_shape(b);                                                                               \
     if (sizeof(R) == 4 || L.lpe != 16) {   /* a statically known model (tsim_static.h): instantiated in its own translation unit (fp64: not four environments per wavefront) */ \
-      const int km_ = kernel_mode(b);                                                                                     \
+      const int km_ = (km);                                                                                               \
       if (km_ == TS_KM_STATIC) { ts_static_pusher_launch(__VA_ARGS__, L.lpe, L.grid, L.lds, st); break; }                 \
       if (km_ == TS_KM_PARAM) { ts_param_pusher_launch(__VA_ARGS__, L.lpe, L.grid, L.lds, st); break; }                   \
     }                                                                                                                     \
@@ -798,6 +801,13 @@ void ts_param_pusher_launch(const BwdArgs<double>& a, double* zsave, int lpe, un
     else if (b->nr <= 8) TS_LAUNCH_L(KERNEL, R, 8, L, st, __VA_ARGS__);                                                  \
     else TS_LAUNCH_L(KERNEL, R, 16, L, st, __VA_ARGS__);                                                                 \
   } while (0)
+
+// does a simulation launch in kernel mode km run a fused static instantiation (TS_LAUNCH; POLICY: TS_LAUNCH_POLICY, tsim_env_push.h)
+static bool launches_fused(const tsim_batch* b, int km, size_t esz, bool policy) {
+  if (km == TS_KM_GENERIC) return false;
+  const int lpe = launch_shape(b).lpe;
+  return policy ? (esz == 4 && lpe == 16) : (esz == 4 || lpe != 16);
+}
 
 // Pads too large for the in-kernel read-out (lanes of one environment over its taxels) are read on demand by tsim_readout; for those
 // the forward launch leaves the pose records of its final state (k_forward, end of the launch).  Not under stream capture: a graph
@@ -878,7 +888,10 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   a.lockstep = b->ab_lockstep ? 1 : 0;
   if (a.lockstep) a.free_run = 0;
   a.default_opts = default_options(b) ? 1 : 0;
-  { KtScope kt_(b, TSIM_KT_FORWARD, st); TS_LAUNCH(k_forward, R, b, st, a); }
+  a.tk = b->tape_k;
+  const int km = kernel_mode(b);
+  if (b->record && !launches_fused(b, km, sizeof(R), false)) b->tape_k_ok = 0;      // records without K from here on
+  { KtScope kt_(b, TSIM_KT_FORWARD, st); TS_LAUNCH(k_forward, R, b, km, st, a); }
   HIPCHK(hipGetLastError());
   if (defer) { KtScope kt_(b, TSIM_KT_TAXELS, st); if (launch_taxels<R>(b, b->fposeR, b->fposeD, nframes, tac_slot, tac_out, st)) return 1; }
   b->pose_valid = emit ? 1 : 0;
@@ -913,7 +926,7 @@ static int launch_param_grad(tsim_batch* b, int n, int seed_stride, int frames, 
   p.seed_stride = seed_stride; p.frames = frames; p.tac_slot = tac_slot; p.tape = (const R*)b->tape; p.z = (const R*)b->zbuf;
   p.df_dtac = (const R*)df_dtac; p.nchunk = pg_chunks_for(b, n); p.chunk_len = (n + p.nchunk - 1) / p.nchunk;
   p.nchunk = (n + p.chunk_len - 1) / p.chunk_len;          // (no empty chunk)
-  p.P = ts_pg_count(npair, nsensor, b->nr); p.part = (R*)b->pgpart; p.stage_cpt = b->stage_cpt;
+  p.P = ts_pg_count(npair, nsensor, b->nr); p.part = (R*)b->pgpart; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
   if (p.nchunk > b->pg_chunks) return fail("param_grad: partial-sum buffer too small");
   const LaunchShape L = launch_shape(b);
   const int ns = TS_WAVE / (b->has_exp ? TS_WAVE : L.lpe);
@@ -933,12 +946,14 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
   a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.n = n; a.t_end = b->t_cur; a.seed_stride = seed_stride; a.frames = frames; a.tac_slot = tac_slot;
   a.tape = (const R*)b->tape; a.df_dq = (const R*)df_dq; a.df_dvar = (const R*)df_dvar; a.df_dtac = (const R*)df_dtac;
   a.lamq = (R*)b->lamq; a.lamv = (R*)b->lamv; a.df_du = (R*)df_du; a.stage_cpt = b->stage_cpt; a.cyc = b->bwd_stamps; a.cull = b->pair_cull;
+  a.tk = b->tape_k;
   {
     KtScope kt_(b, TSIM_KT_BACKWARD, st);
     const int keep_ = b->lpe_forced;
     if (b->ab_bwd_lpe) b->lpe_forced = b->ab_bwd_lpe;      // A/B (TSIM_BWD_LPE at creation): another launch shape for the adjoint kernel (the tape does not depend on it)
-    if (b->dLdp) TS_LAUNCH(k_backward_z, R, b, st, a, (R*)b->zbuf);      // the same variant's SAVEZ twin: z of every sub-step for the parameter pass
-    else TS_LAUNCH(k_backward, R, b, st, a);
+    const int km = b->tape_k_ok ? kernel_mode(b) : TS_KM_GENERIC;      // the fused adjoint reads K from the tape: only where the forward wrote it
+    if (b->dLdp) TS_LAUNCH(k_backward_z, R, b, km, st, a, (R*)b->zbuf);      // the same variant's SAVEZ twin: z of every sub-step for the parameter pass
+    else TS_LAUNCH(k_backward, R, b, km, st, a);
     b->lpe_forced = keep_;
   }
   HIPCHK(hipGetLastError());
@@ -974,7 +989,6 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   b->I.assign(I, I + I[TSIM_IH_NI]); b->F.assign(F, F + I[TSIM_IH_NF]);
   b->nl = nl; b->nr = nr; b->nu = nu; b->nvar = I[TSIM_IH_NVAR]; b->ntax = I[TSIM_IH_NTAXEL];
   b->esz = dtype == TSIM_F32 ? 4 : 8;
-  b->rec = ts_rec(nr, nu, (int)b->esz);
   b->t_cur = 0; b->record = 0; b->has_exp = n_exp > 0;
   b->dFenv = nullptr; b->nfrec = I[TSIM_IH_FOFF_CPT];
   b->lpe_forced = 0;
@@ -998,6 +1012,8 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   }
   b->stage_cpt = 0;
   detect_static_model(b);      // before the staging decision: the launch shape depends on which kernels run
+  b->tape_k = kernel_mode(b) != TS_KM_GENERIC ? 1 : 0;
+  b->rec = ts_rec(nr, nu, (int)b->esz, b->tape_k);
   if (lds_bytes_for(b, 1) > 64 * 1024) { delete b; return fail("model needs more than 64 KiB of LDS per environment"); }
   decide_stage_cpt(b);
   b->dI = nullptr; b->dF = nullptr; b->tape = nullptr; b->lamq = nullptr; b->lamv = nullptr; b->evals = nullptr; b->order = nullptr; b->order_valid = 0; b->prev = nullptr; b->has_prev = 0; b->poseR = nullptr; b->poseD = nullptr; b->nspt = b->I[TSIM_IH_NSPRIM];
@@ -1200,7 +1216,7 @@ int tsim_reset(tsim_batch* b, const void* q0, const void* qd0, int backward_flag
   else hipLaunchKernelGGL(k_set_state<double>, dim3(grd), dim3(blk), 0, st, (double*)b->tape, (const double*)q0, (const double*)qd0, b->B, b->nr, b->rec);
   HIPCHK(hipGetLastError());
   if (zero_async(b->lamq, (size_t)2 * b->B * b->nr * b->esz, st) || zero_async(b->lamv, (size_t)2 * b->B * b->nr * b->esz, st)) return 1;
-  b->t_cur = 0; b->record = backward_flag ? 1 : 0; b->order_valid = 0; b->has_prev = 0;
+  b->t_cur = 0; b->record = backward_flag ? 1 : 0; b->order_valid = 0; b->has_prev = 0; b->tape_k_ok = b->tape_k;
   pose_invalidate(b, st);
   return 0;
 }
@@ -1257,11 +1273,11 @@ int tsim_readout(tsim_batch* b, void* var_out, void* tac_out, void* stream) {
   }
   const bool fk = var_out || !tac || !b->pose_valid;      // the forward launch left the pose records of this state: k_taxels alone
   if (b->dtype == TSIM_F32) {
-    ReadArgs<float> a{b->dI, (const float*)b->dF, (const float*)b->dFenv, b->nfrec, b->B, b->t_cur, (const float*)b->tape, (float*)var_out, tac ? (float*)b->poseR : nullptr, b->poseD, b->nspt, b->stage_cpt};
+    ReadArgs<float> a{b->dI, (const float*)b->dF, (const float*)b->dFenv, b->nfrec, b->B, b->t_cur, (const float*)b->tape, (float*)var_out, tac ? (float*)b->poseR : nullptr, b->poseD, b->nspt, b->stage_cpt, b->tape_k};
     if (fk) hipLaunchKernelGGL(k_readout<float>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), st, a);
     if (tac) { KtScope kt_(b, TSIM_KT_TAXELS, st); if (launch_taxels<float>(b, b->poseR, b->poseD, 1, nullptr, tac_out, st)) return 1; }
   } else {
-    ReadArgs<double> a{b->dI, (const double*)b->dF, (const double*)b->dFenv, b->nfrec, b->B, b->t_cur, (const double*)b->tape, (double*)var_out, tac ? (double*)b->poseR : nullptr, b->poseD, b->nspt, b->stage_cpt};
+    ReadArgs<double> a{b->dI, (const double*)b->dF, (const double*)b->dFenv, b->nfrec, b->B, b->t_cur, (const double*)b->tape, (double*)var_out, tac ? (double*)b->poseR : nullptr, b->poseD, b->nspt, b->stage_cpt, b->tape_k};
     if (fk) hipLaunchKernelGGL(k_readout<double>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), st, a);
     if (tac) { KtScope kt_(b, TSIM_KT_TAXELS, st); if (launch_taxels<double>(b, b->poseR, b->poseD, 1, nullptr, tac_out, st)) return 1; }
   }
@@ -1344,7 +1360,7 @@ int tsim_cache_save(tsim_batch* b, void* stream) {
   // record t0 - 1, so a forward launch that continues on the spare buffer must find it there
   if (b->I[TSIM_IH_INTEGRATOR] == 2 && b->t_cur >= 1)
     HIPCHK(hipMemcpyAsync((char*)spare + off - rec_bytes, (char*)b->tape + off - rec_bytes, rec_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  CacheEntry e; e.buf = b->tape; e.len = b->t_cur; e.record = b->record;
+  CacheEntry e; e.buf = b->tape; e.len = b->t_cur; e.record = b->record; e.tape_k_ok = b->tape_k_ok;
   b->cache.push_back(e);
   b->tape = spare;
   return 0;
@@ -1355,7 +1371,7 @@ int tsim_cache_pop(tsim_batch* b, void* stream) {
   CacheEntry e = b->cache.back(); b->cache.pop_back();
   b->pool.push_back(b->tape);                 // stream order keeps earlier kernels on the old buffer safe: it is only
   b->tape = e.buf;                            // handed out again by a later save on the same stream
-  b->t_cur = e.len; b->record = e.record; b->has_prev = 0; b->order_valid = 0;
+  b->t_cur = e.len; b->record = e.record; b->tape_k_ok = e.tape_k_ok; b->has_prev = 0; b->order_valid = 0;
   pose_invalidate(b, (hipStream_t)stream);
   if (zero_async(b->lamq, (size_t)2 * b->B * b->nr * b->esz, (hipStream_t)stream) || zero_async(b->lamv, (size_t)2 * b->B * b->nr * b->esz, (hipStream_t)stream)) return 1;
   return 0;
@@ -1375,10 +1391,10 @@ int tsim_debug_signature(tsim_batch* b, int t_first, int n, uint32_t* out, void*
   if (!out) return fail("debug_signature: out is null");
   TS_DEVICE(b);
   if (b->dtype == TSIM_F32) {
-    SigArgs<float> a{b->dI, (const float*)b->dF, (const float*)b->dFenv, b->nfrec, b->B, t_first, n, (const float*)b->tape, out, b->stage_cpt};
+    SigArgs<float> a{b->dI, (const float*)b->dF, (const float*)b->dFenv, b->nfrec, b->B, t_first, n, (const float*)b->tape, out, b->stage_cpt, b->tape_k};
     hipLaunchKernelGGL(k_signature<float>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), (hipStream_t)stream, a);
   } else {
-    SigArgs<double> a{b->dI, (const double*)b->dF, (const double*)b->dFenv, b->nfrec, b->B, t_first, n, (const double*)b->tape, out, b->stage_cpt};
+    SigArgs<double> a{b->dI, (const double*)b->dF, (const double*)b->dFenv, b->nfrec, b->B, t_first, n, (const double*)b->tape, out, b->stage_cpt, b->tape_k};
     hipLaunchKernelGGL(k_signature<double>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), (hipStream_t)stream, a);
   }
   HIPCHK(hipGetLastError());

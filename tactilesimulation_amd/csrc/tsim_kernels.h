@@ -17,14 +17,17 @@ template <class MS, class C> __device__ __forceinline__ int ts_integrator(const 
 template <class MS> constexpr int ts_static_nr() { if constexpr (std::is_void<MS>::value) return 0; else return MS::Iv(TSIM_IH_NR); }
 
 // tape record per (sub-step, env), in reals: q[nr] as DOUBLE (the pose chain is double also in the fp32 kernels),
-// qd[nr], H[nr*nr], u[nu]; padded to an even count so that every record starts 8-byte aligned
+// qd[nr], H[nr*nr], u[nu] and, with tk (a batch whose model has a fused static instantiation, tsim_hip.hip tsim_batch_create), K[nr*nr]: the
+// position partial (dr/dq) / ca at the same iterate as H, which the fused adjoint kernel takes instead of evaluating the contacts again;
+// padded to an even count so that every record starts 8-byte aligned
 __host__ __device__ inline int ts_qw(int esz) { return 8 / esz; }                      // reals per double
-__host__ __device__ inline int ts_rec(int nr, int nu, int esz) { return (ts_qw(esz) * nr + nr + nr * nr + nu + 1) & ~1; }
+__host__ __device__ inline int ts_rec(int nr, int nu, int esz, int tk) { return (ts_qw(esz) * nr + nr + nr * nr + nu + (tk ? nr * nr : 0) + 1) & ~1; }
 template <class R> __device__ __forceinline__ double* rec_q(R* rec) { return reinterpret_cast<double*>(rec); }
 template <class R> __device__ __forceinline__ const double* rec_q(const R* rec) { return reinterpret_cast<const double*>(rec); }
 template <class R> __device__ __forceinline__ int rec_qd(int nr) { return ts_qw((int)sizeof(R)) * nr; }           // offset of qd
 template <class R> __device__ __forceinline__ int rec_H(int nr) { return ts_qw((int)sizeof(R)) * nr + nr; }
 template <class R> __device__ __forceinline__ int rec_u(int nr) { return ts_qw((int)sizeof(R)) * nr + nr + nr * nr; }
+template <class R> __device__ __forceinline__ int rec_K(int nr, int nu) { return ts_qw((int)sizeof(R)) * nr + nr + nr * nr + nu; }
 
 // ================================================================================================ read-out
 // variables: lanes = end-effector points; tactile: lanes = taxels (coalesced SoA loads of position / frame,
@@ -93,6 +96,7 @@ enum { TP_R_SIZE = 18, TP_D_SIZE = 12 };      // pose record of a (sensor, primi
 template <class R> struct FwdArgs {
   const int* I; const R* F; const R* Fenv; int fstride;
   int B, nsub, record, t0;
+  int tk = 0;             // the tape records hold K (ts_rec): the fused static instantiations write it
   int nframes;            // env-steps in this launch; frame f reads u[f][B][nu] and writes *_out[f][B][...] (tsim_rollout)
   const int* tac_slot;    // [nframes] slot of frame f in tac_out, < 0: no tactile read-out for that frame; null: slot f
   R* tape; const R* u;
@@ -144,7 +148,7 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
   const int env = a.order ? a.order[min(eidx, a.B - 1)] : min(eidx, a.B - 1);
   Ctx<R> c; ctx_init<R, MS>(c, a.I, a.F, lds, NS, slot, lane, LPE, a.stage_cpt != 0, a.Fenv ? a.Fenv + (size_t)env * a.fstride : nullptr);
   c.cull = a.cull;
-  const int nr = c.nr, nu = c.nu, REC = ts_rec(nr, nu, (int)sizeof(R));
+  const int nr = c.nr, nu = c.nu, REC = ts_rec(nr, nu, (int)sizeof(R), a.tk);
   init_world(c, lane, LPE);
   {
     const R* st = a.tape + ((size_t)a.t0 * a.B + env) * REC;
@@ -472,6 +476,9 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
         if (lane < nr) { rec_q(rec)[lane] = c.qD[lane]; rec[rec_qd<R>(nr) + lane] = c.qd[lane]; }
         for (int e = lane; e < nr * nr; e += LPE) rec[rec_H<R>(nr) + e] = c.H[e];
         if (lane < nu) rec[rec_u<R>(nr) + lane] = c.u[lane];
+        // K of the same evaluation as H (evaluate_static_fused: c.H2).  A commit always follows this slot's OWN evaluation with tangents of
+        // the committed point while recording (judge: a helper's result is adopted only when a Newton step follows), so c.H and c.H2 match
+        if constexpr (ts_static_fused<MS, R>()) { if (a.tk) for (int e = lane; e < nr * nr; e += LPE) rec[rec_K<R>(nr, nu) + e] = c.H2[e]; }
       }
       TS_SYNC();
       if (lane < nr) {
@@ -566,6 +573,7 @@ template <class R, int LPE, class MS> __device__ __forceinline__ void ts_static_
 template <class R> struct BwdArgs {
   const int* I; const R* F; const R* Fenv; int fstride;
   int B, n, t_end;
+  int tk = 0;             // the tape records hold K (ts_rec); the fused static instantiations are launched only on a tape whose K the forward wrote
   int seed_stride;        // sub-step j (0 = oldest of the n) carries direct loss partials iff (j + 1) % seed_stride == 0
   int frames;             // 0: seeds [B][n / seed_stride][.], df_du [B][n][nu] per sub-step (tsim_backward_steps)
                           // 1: seeds [n / seed_stride][B][.], df_du [n / seed_stride][B][nu] summed per env-step (tsim_backward_episode)

@@ -12,7 +12,7 @@
   // launch, round 6; the forward kernel gains 5 % from the same fold)
   Ctx<R> c; ctx_init<R, MS>(c, a.I, a.F, lds, NS, slot, lane, LPE, a.stage_cpt != 0, a.Fenv ? a.Fenv + (size_t)env * a.fstride : nullptr);
   c.cull = a.cull;
-  const int nr = c.nr, nu = c.nu, REC = ts_rec(nr, nu, (int)sizeof(R));
+  const int nr = c.nr, nu = c.nu, REC = ts_rec(nr, nu, (int)sizeof(R), a.tk);
   const int nvar3 = 3 * c.nvar, ntac3 = 3 * c.ntax;
   R* H2 = c.H2;    // taped Newton matrix of the sub-step
   init_world(c, lane, LPE);
@@ -28,13 +28,20 @@
   TS_SYNC();
   R du_frame = R(0);
   R pol_dq = R(0); bool pol_have = false;      // POLICY: what the NEXT frame's observation put on this frame's final state (q[0..2]; tactile: pol.dobs_tac)
-  // The tape record of sub-step t (q1, qd1, u, H) and the state before it (q, qd of record t - 1) are fetched ONE ITERATION AHEAD
+  // A statically known model (tsim_static_eval.h): no evaluation at all — the tape holds, next to H, the position partial K of the same
+  // iterate (k_forward), so y_q = K^T z is a product and M z a value-only link sweep (the evaluation of the taped point with tangents, pairs
+  // and point loops it replaces cost as much as a forward evaluation round).  Only a sub-step that carries a loss seed needs the link
+  // states with tangents (ts_static_output_vjp runs its own sweep).
+  constexpr bool kFused = ts_static_fused<MS, R>();
+  // The tape record of sub-step t (q1, qd1, u, H, K) and the state before it (q, qd of record t - 1) are fetched ONE ITERATION AHEAD
   // into registers: a lone wavefront cannot hide the ~2 x 1.5 k cycles of HBM latency of dependent loads at the top of every
   // sub-step, but the loads for the next sub-step fly during the whole of this one.  (Record t - 1 supplies q0, qd0 now and
-  // q1, qd1 of the next iteration, so each iteration fetches u, H of record t - 1 and q, qd of record t - 2.)
+  // q1, qd1 of the next iteration, so each iteration fetches u, H, K of record t - 1 and q, qd of record t - 2.)
   constexpr int NHL = (NRM * NRM + LPE - 1) / LPE;
-  const int oqd = rec_qd<R>(nr), oH = rec_H<R>(nr), ou = rec_u<R>(nr);
+  const int oqd = rec_qd<R>(nr), oH = rec_H<R>(nr), ou = rec_u<R>(nr), oK = rec_K<R>(nr, nu);
   double pq1 = 0.0, pq0 = 0.0; R pqd1 = R(0), pqd0 = R(0), pqdm = R(0), pu = R(0), pH[NHL];     // pqdm: qd two records back (BDF2)
+  R pK[kFused ? NHL : 1];
+  R* KT = c.H;      // the fused path's taped K of the sub-step (c.H is not used otherwise there)
   {
     const R* r1 = a.tape + ((size_t)a.t_end * a.B + env) * REC;
     const R* r0 = a.tape + ((size_t)(a.t_end - 1) * a.B + env) * REC;
@@ -43,6 +50,10 @@
     if (lane < nu) pu = r1[ou + lane];
 #pragma unroll
     for (int i = 0; i < NHL; ++i) { const int e = lane + i * LPE; pH[i] = e < nr * nr ? r1[oH + e] : R(0); }
+    if constexpr (kFused) {
+#pragma unroll
+      for (int i = 0; i < NHL; ++i) { const int e = lane + i * LPE; pK[i] = (a.tk && e < nr * nr) ? r1[oK + e] : R(0); }
+    }
   }
   for (int j = a.n - 1; j >= 0; --j) {
     const int t = a.t_end - (a.n - 1 - j);
@@ -58,6 +69,10 @@
     if (lane < nu) c.u[lane] = pu;
 #pragma unroll
     for (int i = 0; i < NHL; ++i) { const int e = lane + i * LPE; if (e < nr * nr) H2[e] = pH[i]; }
+    if constexpr (kFused) {
+#pragma unroll
+      for (int i = 0; i < NHL; ++i) { const int e = lane + i * LPE; if (e < nr * nr) KT[e] = pK[i]; }
+    }
     TS_STAMP(c);
     if (j > 0) {                                      // next iteration: sub-step t - 1
       const R* r1 = a.tape + ((size_t)(t - 1) * a.B + env) * REC;
@@ -68,6 +83,10 @@
       if (lane < nu) pu = r1[ou + lane];
 #pragma unroll
       for (int i = 0; i < NHL; ++i) { const int e = lane + i * LPE; pH[i] = e < nr * nr ? r1[oH + e] : R(0); }
+      if constexpr (kFused) {
+#pragma unroll
+        for (int i = 0; i < NHL; ++i) { const int e = lane + i * LPE; pK[i] = (a.tk && e < nr * nr) ? r1[oK + e] : R(0); }
+      }
     }
     // (the loads above must be ISSUED here, a whole sub-step ahead of their use: with the model's sizes as compile-time constants the scheduler
     // otherwise sinks them to the top of the next iteration and a lone wavefront waits ~2 us of HBM latency per sub-step — measured in round 6:
@@ -75,10 +94,6 @@
     __builtin_amdgcn_sched_barrier(0);
     TS_SYNC();
     TS_STAMP(c);
-    // A statically known model (tsim_static_eval.h): the evaluation at the taped state is one register-resident pass AFTER the adjoint solve
-    // and returns this lane's (H^T z, M z) — no records, no c.H.  Only a sub-step that carries a loss seed needs link records in LDS
-    // (output_vjp reads them): it runs the link sweep alone first.
-    constexpr bool kFused = ts_static_fused<MS, R>();
     const bool seeded = (j + 1) % a.seed_stride == 0;
     if constexpr (kFused) { }      // (a seeded sub-step runs its own link sweep inside ts_static_output_vjp)
     else if constexpr (std::is_void<MS>::value) phase1<R, true, EXPJ>(c, lane, R(1), R(0), R(0));
@@ -107,7 +122,11 @@
     }
     TS_SYNC();
     evaluate<R, NRM, EXPJ, LPE, MS>(c, lane, R(1), c.cv, c.ca, true);
-    for (int e = lane; e < nr * nr; e += LPE) H2[e] = c.H[e];
+    for (int e = lane; e < nr * nr; e += LPE) {
+      const R h_ = c.H[e];
+      if constexpr (kFused) KT[e] = H2[e];      // the fused evaluation leaves K in c.H2
+      H2[e] = h_;
+    }
     TS_SYNC();
 #endif
     if (lane < nr) c.rhs[lane] = c.lamq[lane] + c.cv * c.lamv[lane];      // d qd1 / d q1 = cv
@@ -124,7 +143,12 @@
       if (lane < nr) for (int i = 0; i < nr; ++i) yq += c.z[i] * c.H[i * nr + lane];
     } else {
       TS_STAMP(c);
-      evaluate_static_fused_adjoint<R, NRM, LPE, MS>(c, lane, yq, ym);
+      ym = ts_static_mass_times_z<R, MS>(c, lane);      // (its barriers also order the solve's z before the product below)
+      constexpr int NRS = ts_static_nr<MS>();
+      if (lane < NRS) {
+#pragma unroll
+        for (int i = 0; i < NRS; ++i) yq += c.z[i] * KT[i * NRS + lane];
+      }
       TS_STAMP(c);
     }
     TS_STAMP(c);

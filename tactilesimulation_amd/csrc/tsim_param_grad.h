@@ -21,6 +21,7 @@ template <class R> struct PgArgs {
   int P;                                             // ts_pg_count
   R* part;                                           // [nchunk][B][P] partial sums
   int stage_cpt;
+  int tk;                                            // the tape records hold K (ts_rec)
 };
 template <class R> struct PgReduceArgs {
   const R* part; int nchunk, B, P;

@@ -28,7 +28,7 @@ __global__ void __launch_bounds__(TS_WAVE) k_param_grad(PgArgs<R> a) {
   const bool valid = e_ < a.B;                                 // an idle slot of a chunk's last block repeats the last environment and stores nothing
   const int env = min(e_, a.B - 1);
   Ctx<R> c; ctx_init<R>(c, a.I, a.F, lds, NS, slot, lane, LPE, a.stage_cpt != 0, a.Fenv ? a.Fenv + (size_t)env * a.fstride : nullptr);
-  const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R));
+  const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R), a.tk);
   const int npair = c.npair, nsensor = c.nsensor, ntac3 = 3 * c.ntax;
   init_world(c, lane, LPE);
   R* out = a.part + ((size_t)chunk * a.B + env) * a.P;

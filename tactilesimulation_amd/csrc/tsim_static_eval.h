@@ -13,8 +13,8 @@
 //   * the point loop (pair_points_matrix, the same code as the generic kernels') reduces to the 6 x 12 matrix in every lane; lane k
 //     applies it to ITS 12-vector, brings the wrench and its tangent to the world frame and adds them to its per-link accumulators;
 //   * the leaf -> root pass is a compile-time loop over the levels on those accumulators; the parents are constants.
-// What still goes to LDS is the result — g and H in the forward kernel (the solve and the tape read them), nothing in the adjoint kernel
-// (it takes H^T z and M z back in registers) — and, once per frame, the link value records the read-out reads (ts_static_value_records).
+// What still goes to LDS is the result — g, H and the position partial K (the solve and the tape read them) — and, once per frame, the link
+// value records the read-out reads (ts_static_value_records).  The adjoint kernel evaluates no contact at all: H and K come from the tape.
 // An evaluation round of four environments (fine stamps, profiles/r04_static_model.md): 37.7 k -> 17.1 k cycles.
 #pragma once
 
@@ -46,9 +46,10 @@ __device__ __forceinline__ void ts_fused_pair_pose(const Ctx<R>& c, const TsLink
   P.RPA = cvtm<R>(P.RPAd); P.pPA = cvt3<R>(P.pPAd); P.wrel = Vrel.a; P.vrel = Vrel.l;
 }
 
-// pair PK of the static model: pose, this lane's 12-vector, the point loop, the fold into the lane's per-link wrench accumulators
+// pair PK of the static model: pose, this lane's 12-vector (direction k), the point loop (lanes = points), the fold into the lane's per-link
+// wrench accumulators
 template <class R, int NRM, int LPE, class MS, int PK>
-__device__ __forceinline__ void ts_fused_pair(const Ctx<R>& c, int lane, R sq, const TsLinkState<R>* st, const S6<R>& Wk, S6<R>* Fl, S6<R>* dFl, bool tang = true) {
+__device__ __forceinline__ void ts_fused_pair(const Ctx<R>& c, int lane, int k, R sq, const TsLinkState<R>* st, const S6<R>& Wk, S6<R>* Fl, S6<R>* dFl, bool tang = true) {
   using T = TsTopo<MS>;
   constexpr int NP = MS::Iv(TSIM_IH_NPAIR);
   if constexpr (PK < NP) {
@@ -56,19 +57,20 @@ __device__ __forceinline__ void ts_fused_pair(const Ctx<R>& c, int lane, R sq, c
     constexpr int flags = MS::Iv(o + TSIM_PI_FLAGS), prim = MS::Iv(o + TSIM_PI_PRIM), npt = MS::Iv(o + TSIM_PI_NPT), pt0 = MS::Iv(o + TSIM_PI_PT0);
     constexpr int la = MS::Iv(o + TSIM_PI_LINKA), lb = MS::Iv(o + TSIM_PI_LINKB);
     if constexpr ((flags & 1) != 0) {
-      const int k = lane;
       R pf[TSIM_PF_SIZE];
       M3<R> RP; V3<R> pP; PairPose<R> P; S6<R> Vrel, dVA, dVB;
       ts_fused_pair_pose<R, MS, PK>(c, st, pf, RP, pP, P, Vrel, dVA, dVB);
       // ---- this lane's direction (pair_stage_tangent, vmode 0): relative displacement and d(relative twist) in the primitive's frame
       constexpr int ancA = la != 0 ? T::li(la == 0 ? 1 : la, TSIM_LI_ANCMASK) : 0, ancB = lb != 0 ? T::li(lb == 0 ? 1 : lb, TSIM_LI_ANCMASK) : 0;
       const R inA = ((ancA >> k) & 1) ? R(1) : R(0), inB = ((ancB >> k) & 1) ? R(1) : R(0);
-      // ---- lanes = contact points
+      // ---- lanes = contact points.  At most 8 points: every 8-lane half of the slot evaluates all of them (lane l point l mod 8) and sums them
+      // over the half — the same operands in the same order, so lanes NRM.. (the K columns' directions, evaluate_static_fused) hold the bits
+      // lanes 0..7 hold, for no instruction more
+      constexpr bool kHalfRow = npt <= 8 && NRM <= 8;
       R w0[6], M[6][12];
-      const bool any_hit = pair_points_matrix<R, LPE, prim, flags>(c, pt0, npt, prim, (flags & 2) != 0, pf, P, lane, w0, M, tang);
+      const bool any_hit = pair_points_matrix<R, LPE, prim, flags>(c, pt0, npt, prim, (flags & 2) != 0, pf, P, kHalfRow ? (lane & 7) : lane, w0, M, tang);
       TS_STAMP2(c);
       if (any_hit) {
-        constexpr bool kHalfRow = npt <= 8 && NRM <= 8;      // all points (and all directions) in the first 8 lanes of the slot
         if constexpr (kHalfRow) {
 #pragma unroll
           for (int e = 0; e < 6; ++e) w0[e] = half_row_sum(w0[e]);
@@ -107,7 +109,7 @@ __device__ __forceinline__ void ts_fused_pair(const Ctx<R>& c, int lane, R sq, c
       } else TS_STAMP2(c);
       TS_STAMP2(c);
     }
-    ts_fused_pair<R, NRM, LPE, MS, PK + 1>(c, lane, sq, st, Wk, Fl, dFl, tang);
+    ts_fused_pair<R, NRM, LPE, MS, PK + 1>(c, lane, k, sq, st, Wk, Fl, dFl, tang);
   }
 }
 
@@ -146,54 +148,52 @@ __device__ __forceinline__ R ts_fused_joint_space(const Ctx<R>& c, R sq, R sv, R
   return hjj;
 }
 
-// dof JJ of link LINK in the leaf -> root pass: tau_j = W_j . F, its tangent (column k of H, lane k), the joint-space forces
-// ADJ: the adjoint kernel's use — nothing is stored; lane k accumulates yq_k = sum_j z_j H[j][k] over its column as it is produced
-template <class R, class MS, int LINK, int JJ, bool ADJ>
-__device__ __forceinline__ void ts_fused_dof(const Ctx<R>& c, int k, R sq, R sv, R h2, R mv, const S6<R>& Wj, const S6<R>& Wk, const S6<R>& F, const S6<R>& dF, const R* zr, R& yq, bool tang) {
+// dof JJ of link LINK in the leaf -> root pass: tau_j = W_j . F, its tangent (column k of the lane's matrix), the joint-space forces.  The lane
+// stores its entry at c.H[j * nr + col] when `col` >= 0: column k of H (lanes 0..nr-1) or of K (lanes NRM..NRM+nr-1, col points into c.H2)
+template <class R, class MS, int LINK, int JJ>
+__device__ __forceinline__ void ts_fused_dof(const Ctx<R>& c, int lane, int k, int col, R sq, R sv, R h2, R mv, const S6<R>& Wj, const S6<R>& Wk, const S6<R>& F, const S6<R>& dF, bool tang) {
   using T = TsTopo<MS>;
   constexpr int k0 = T::li(LINK, TSIM_LI_DOF0), ndj = T::li(LINK, TSIM_LI_NDOF), nr = T::NR;
   if constexpr (JJ < ndj) {
     constexpr int j = k0 + JJ;
     R gj = dot6(Wj, F);
     const R hjj = ts_fused_joint_space<R, MS, j>(c, sq, sv, gj);      // damping, limits, motors of this dof
-    if (ADJ || tang) {
+    if (tang) {
       const R dtau = dot6(Wj, dF) + mv * dot6(crm(Wk, Wj), F);
       const R Hjk = dtau * h2 + (k == j ? hjj : R(0)) * h2;      // columns are scaled by 1 / ca (g = r / ca)
-      if constexpr (ADJ) yq += zr[j] * Hjk;
-      else if (k < nr) c.H[j * nr + k] = Hjk;
+      if (col >= 0) c.H[j * nr + col] = Hjk;
     }
-    if constexpr (!ADJ) { if (k == 0) c.g[j] = gj * h2; }
+    if (lane == 0) c.g[j] = gj * h2;
   }
 }
 
-// leaf -> root over the lane's accumulators: tau_j = W_j . F_subtree(link(j)), column k of H, the value g (lane 0), a link's subtree
+// leaf -> root over the lane's accumulators: tau_j = W_j . F_subtree(link(j)), column k of H (or K), the value g (lane 0), a link's subtree
 // wrench into its parent's — links of level LEVEL, then the levels above.  The joint-space forces (damping, limits, motors: constants of the
-// dof) go in right here: every lane has the value g_j, lane j adds its diagonal entry
-template <class R, class MS, bool ADJ, int LEVEL, int LINK>
-__device__ __forceinline__ void ts_fused_up_links(const Ctx<R>& c, int lane, R sq, R sv, R h2, const TsLinkTmp<R>* tmp, const S6<R>& Wk, S6<R>* Fl, S6<R>* dFl, const R* zr, R& yq, bool tang) {
+// dof) go in right here: every lane has the value g_j, the lanes of direction j add their diagonal entry
+template <class R, class MS, int LEVEL, int LINK>
+__device__ __forceinline__ void ts_fused_up_links(const Ctx<R>& c, int lane, int k, int col, R sq, R sv, R h2, const TsLinkTmp<R>* tmp, const S6<R>& Wk, S6<R>* Fl, S6<R>* dFl, bool tang) {
   using T = TsTopo<MS>;
   if constexpr (LINK <= T::NL) {
     if constexpr (TsLevels<MS>::depth(LINK) == LEVEL) {
       constexpr int i = LINK, par = T::li(i, TSIM_LI_PARENT), ancm = T::li(i, TSIM_LI_ANCMASK);
-      const int k = lane;
       const S6<R> F = Fl[i];
       S6<R> dF = zero6<R>();
       if (tang) dF = dFl[i];
       const S6<R> Wj[3] = {tmp[i].Wj0, tmp[i].Wj1, tmp[i].Wj2};
       const R mv = ((ancm >> k) & 1) ? sq : R(0);          // does dof k move link i (its own joint's dofs included)
-      ts_fused_dof<R, MS, LINK, 0, ADJ>(c, k, sq, sv, h2, mv, Wj[0], Wk, F, dF, zr, yq, tang);
-      ts_fused_dof<R, MS, LINK, 1, ADJ>(c, k, sq, sv, h2, mv, Wj[1], Wk, F, dF, zr, yq, tang);
-      ts_fused_dof<R, MS, LINK, 2, ADJ>(c, k, sq, sv, h2, mv, Wj[2], Wk, F, dF, zr, yq, tang);
+      ts_fused_dof<R, MS, LINK, 0>(c, lane, k, col, sq, sv, h2, mv, Wj[0], Wk, F, dF, tang);
+      ts_fused_dof<R, MS, LINK, 1>(c, lane, k, col, sq, sv, h2, mv, Wj[1], Wk, F, dF, tang);
+      ts_fused_dof<R, MS, LINK, 2>(c, lane, k, col, sq, sv, h2, mv, Wj[2], Wk, F, dF, tang);
       if constexpr (par != 0) { Fl[par] = Fl[par] + F; if (tang) dFl[par] = dFl[par] + dF; }
     }
-    ts_fused_up_links<R, MS, ADJ, LEVEL, LINK + 1>(c, lane, sq, sv, h2, tmp, Wk, Fl, dFl, zr, yq, tang);
+    ts_fused_up_links<R, MS, LEVEL, LINK + 1>(c, lane, k, col, sq, sv, h2, tmp, Wk, Fl, dFl, tang);
   }
 }
-template <class R, class MS, bool ADJ, int LEVEL>
-__device__ __forceinline__ void ts_fused_up(const Ctx<R>& c, int lane, R sq, R sv, R h2, const TsLinkTmp<R>* tmp, const S6<R>& Wk, S6<R>* Fl, S6<R>* dFl, const R* zr, R& yq, bool tang = true) {
+template <class R, class MS, int LEVEL>
+__device__ __forceinline__ void ts_fused_up(const Ctx<R>& c, int lane, int k, int col, R sq, R sv, R h2, const TsLinkTmp<R>* tmp, const S6<R>& Wk, S6<R>* Fl, S6<R>* dFl, bool tang) {
   if constexpr (LEVEL >= 0) {
-    ts_fused_up_links<R, MS, ADJ, LEVEL, 1>(c, lane, sq, sv, h2, tmp, Wk, Fl, dFl, zr, yq, tang);
-    ts_fused_up<R, MS, ADJ, LEVEL - 1>(c, lane, sq, sv, h2, tmp, Wk, Fl, dFl, zr, yq, tang);
+    ts_fused_up_links<R, MS, LEVEL, 1>(c, lane, k, col, sq, sv, h2, tmp, Wk, Fl, dFl, tang);
+    ts_fused_up<R, MS, LEVEL - 1>(c, lane, k, col, sq, sv, h2, tmp, Wk, Fl, dFl, tang);
   }
 }
 template <class R, class MS, int LINK>
@@ -204,28 +204,35 @@ __device__ __forceinline__ void ts_fused_link_wrenches(const TsLinkState<R>* st,
   }
 }
 
-// phases 1 - 3 of one evaluation (what evaluate() runs between setting q / qd / qa and returning g, H).  RECORDS: the link value records
-// (with the COM / inertia entries), the joint screws and the twist tangents are left in LDS as well, for code that reads them there (A/B
-// only: the forward kernel's read-out needs the value records of a frame's FINAL state only and writes them then, ts_static_value_records —
-// 105 LDS store instructions less in every evaluation round; the adjoint kernel has its own pass, evaluate_static_fused_adjoint, and
-// ts_static_output_vjp for the seeded sub-steps: no records at all).
-template <class R, int NRM, int LPE, class MS, bool RECORDS>
+// phases 1 - 3 of one evaluation (what evaluate() runs between setting q / qd / qa and returning g, H).  Nothing but g and H goes to LDS: the
+// forward kernel's read-out needs the value records of a frame's FINAL state only and writes them then (ts_static_value_records — 105 LDS
+// store instructions less in every evaluation round); the adjoint kernel reads the matrices from the tape.
+// Two channels of directions per slot: lane l computes the tangent w.r.t. dof k = l mod NRM with the seeds (sq, sv, sa) — column k of
+// H = dg/dq1, stored by lanes 0..nr-1 — if l < NRM, and with the seeds (1, 0, 0) otherwise — column k of K = (dr/dq) / ca, the position
+// partial alone, stored to c.H2 by lanes NRM..NRM+nr-1: what the adjoint kernel needs next to H (K^T z; tsim_kernels_backward.h), and what the
+// forward kernel tapes with H at a converged iterate.  Those lanes carried no dof before and computed zeros; lanes 0..NRM-1 compute exactly
+// what they did (every cross-lane step of the direction phases reads values of the point phases only, which every lane holds).
+template <class R, int NRM, int LPE, class MS>
 __device__ __forceinline__ void evaluate_static_fused(const Ctx<R>& c, int lane, R sq, R sv, R sa, bool tang = true) {
   using T = TsTopo<MS>;
   static_assert(!T::has_exp() && T::NR <= 16, "static sweep: no rotation-vector joint, at most 16 dofs");
   static_assert(MS::Iv(TSIM_IH_NPAIR) <= 8, "fused static evaluation: the pairs are unrolled");
+  static_assert(T::NR <= NRM && (NRM & (NRM - 1)) == 0 && 2 * NRM <= LPE, "fused static evaluation: two channels of NRM directions per slot");
   TS_SYNC();
+  const int k = lane & (NRM - 1);
+  const bool kch = lane >= NRM;                              // the K channel
+  const R sqk = kch ? R(1) : sq, svk = kch ? R(0) : sv, sak = kch ? R(0) : sa;
+  const int col = k >= T::NR || lane >= 2 * NRM ? -1 : kch ? (int)(c.H2 - c.H) + k : k;
   TsLinkState<R> st[T::NL + 1];
   TsLinkTmp<R> tmp[T::NL + 1];
   S6<R> Wk = zero6<R>(), dFl[T::NL + 1], Fl[T::NL + 1];
-  ts_l_level<R, MS, true, RECORDS, RECORDS ? 1 : 0, 0>(c, lane, sq, sv, sa, st, tmp, Wk, dFl, tang);
+  ts_l_level<R, MS, true, false, 0, 0>(c, k, sqk, svk, sak, st, tmp, Wk, dFl, tang);      // (nothing stored: the lane argument is the direction)
   ts_fused_link_wrenches<R, MS, 1>(st, tmp, Fl);
   TS_STAMP(c);
-  ts_fused_pair<R, NRM, LPE, MS, 0>(c, lane, sq, st, Wk, Fl, dFl, tang);
+  ts_fused_pair<R, NRM, LPE, MS, 0>(c, lane, k, sqk, st, Wk, Fl, dFl, tang);
   TS_STAMP(c);
   const R h2 = R(1) / c.ca;      // g = r / ca  (BDF1: h^2 r)
-  R yq_unused = R(0);
-  ts_fused_up<R, MS, false, TsLevels<MS>::max_depth()>(c, lane, sq, sv, h2, tmp, Wk, Fl, dFl, nullptr, yq_unused, tang);      // ... with the joint-space forces of each dof
+  ts_fused_up<R, MS, TsLevels<MS>::max_depth()>(c, lane, k, col, sqk, svk, h2, tmp, Wk, Fl, dFl, tang);      // ... with the joint-space forces of each dof
   TS_SYNC();
   TS_STAMP2(c);
 }
@@ -272,32 +279,25 @@ __device__ __forceinline__ void ts_mz_up(int lane, const TsLinkTmp<R>* tmp, S6<R
   if constexpr (LEVEL >= 0) { ts_mz_up_links<R, MS, LEVEL, 1>(lane, tmp, f, ym); ts_mz_up<R, MS, LEVEL - 1>(lane, tmp, f, ym); }
 }
 
-// The adjoint kernel's evaluation at a taped state (seeds (1, 0, 0): H = dr/dq / ca) with c.z known: nothing is stored — lane k returns
-//   yq = (H^T z)_k  and  ym = (M z)_k ,  which is all the kernel uses of it.
-template <class R, int NRM, int LPE, class MS>
-__device__ __forceinline__ void evaluate_static_fused_adjoint(const Ctx<R>& c, int lane, R& yq, R& ym) {
+// lane k's (M z)_k at the positions in c.qD (the adjoint kernel, with c.z known): a value-only link sweep — of its values only the joint
+// screws, frames and inertias are used — and the two passes above; nothing is stored
+template <class R, class MS>
+__device__ __forceinline__ R ts_static_mass_times_z(const Ctx<R>& c, int lane) {
   using T = TsTopo<MS>;
   TS_SYNC();
   TsLinkState<R> st[T::NL + 1];
   TsLinkTmp<R> tmp[T::NL + 1];
-  S6<R> Wk = zero6<R>(), dFl[T::NL + 1], Fl[T::NL + 1];
-  ts_l_level<R, MS, true, false, 0, 0>(c, lane, R(1), R(0), R(0), st, tmp, Wk, dFl);
-  ts_fused_link_wrenches<R, MS, 1>(st, tmp, Fl);
-  TS_STAMP(c);
-  ts_fused_pair<R, NRM, LPE, MS, 0>(c, lane, R(1), st, Wk, Fl, dFl);
-  TS_STAMP(c);
+  S6<R> Wk = zero6<R>(), dFl[T::NL + 1];
+  ts_l_level<R, MS, false, false, 0, 0>(c, lane, R(0), R(0), R(0), st, tmp, Wk, dFl);
   R zr[T::NR];
 #pragma unroll
   for (int j = 0; j < T::NR; ++j) zr[j] = c.z[j];
-  const R h2 = R(1) / c.ca;
-  yq = R(0);
-  ts_fused_up<R, MS, true, TsLevels<MS>::max_depth()>(c, lane, R(1), R(0), h2, tmp, Wk, Fl, dFl, zr, yq);
-  TS_STAMP(c);
   S6<R> A[T::NL + 1], f[T::NL + 1];
-  ym = R(0);
+  R ym = R(0);
   ts_mz_down<R, MS, 0>(tmp, zr, A, f);
   ts_mz_up<R, MS, TsLevels<MS>::max_depth()>(lane, tmp, f, ym);
   TS_SYNC();
+  return ym;
 }
 
 // the link value records and joint screws of the state in c.q / c.qd / c.qa (the last evaluation's), for the code that reads them from LDS:

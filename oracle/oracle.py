@@ -73,6 +73,11 @@ def lib(native=False):
         L.orc_residual.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp]
         L.orc_contact_list.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int), _dp]
         L.orc_contact_list.restype = C.c_int
+        L.orc_taxel_list.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int), _dp]
+        L.orc_taxel_list.restype = C.c_int
+        L.orc_set_param_grad.argtypes = [C.c_void_p, _dp]
+        L.orc_table_size.argtypes = [C.c_void_p]
+        L.orc_table_size.restype = C.c_int
         L.orc_inverse_dynamics.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
         L.orc_bench_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]
         L.orc_bench_rollout.restype = C.c_long
@@ -109,6 +114,7 @@ class OracleSim:
         self.nr, self.nu = model.ndof_r, model.ndof_u
         self.nvar, self.ntac = model.ndof_var, model.ndof_tactile
         self.h = model.h
+        self._pg = None
         self.set_solver(solver)
 
     def set_solver(self, solver):
@@ -163,6 +169,19 @@ class OracleSim:
             raise RuntimeError("oracle backward failed (%d)" % rc)
         return du[:n * self.nu].reshape(n, self.nu)
 
+    def set_param_grad(self, buf):
+        """Table gradient, the column convention of BatchSim.set_param_grad for one environment: while `buf` (float64 [table_size], C-contiguous,
+        table_size = the model's per-environment table width, its float records before the contact points) is set, every backward_steps ADDS
+        dL/d(entry) to it for the columns model.param_columns() names and leaves the other columns untouched.  None switches it off.  The
+        oracle keeps a reference to the buffer."""
+        if buf is not None:
+            if not (isinstance(buf, np.ndarray) and buf.dtype == np.float64 and buf.ndim == 1 and buf.flags.c_contiguous):
+                raise TypeError("set_param_grad: a C-contiguous float64 vector")
+            if buf.size < self._L.orc_table_size(self._h):
+                raise ValueError("set_param_grad: %d columns, the tables have %d" % (buf.size, self._L.orc_table_size(self._h)))
+        self._pg = buf
+        self._L.orc_set_param_grad(self._h, _p(buf))
+
     def adjoint(self):
         a, b = np.zeros(self.nr), np.zeros(self.nr)
         self._L.orc_get_adjoint(self._h, _p(a), _p(b))
@@ -193,6 +212,14 @@ class OracleSim:
         od = np.zeros((max_rows, 2))
         n = self._L.orc_contact_list(self._h, _p(_f(q, self.nr)), _p(_f(qd, self.nr)), max_rows, oi.ctypes.data_as(C.POINTER(C.c_int)), _p(od))
         return [(int(oi[i, 0]), int(oi[i, 1]), int(oi[i, 2]), float(od[i, 0]), float(od[i, 1])) for i in range(min(n, max_rows))]
+
+    def taxel_list(self, q, qd, max_rows=4096):
+        """Penetrating (taxel, paired primitive) items of the state (q, qd): [(sensor, taxel, pair, branch, depth, normal velocity, tangential
+        speed)] (diagnostics)."""
+        oi = np.zeros((max_rows, 4), dtype=np.int32)
+        od = np.zeros((max_rows, 3))
+        n = self._L.orc_taxel_list(self._h, _p(_f(q, self.nr)), _p(_f(qd, self.nr)), max_rows, oi.ctypes.data_as(C.POINTER(C.c_int)), _p(od))
+        return [tuple(int(x) for x in oi[i]) + tuple(float(x) for x in od[i]) for i in range(min(n, max_rows))]
 
     def inverse_dynamics(self, q, qd, qdd, u=None):
         r = np.zeros(self.nr)

@@ -142,9 +142,12 @@ template <class T> struct Link {
 // Returns the world-frame force on the point fixed to link A at x_w (and -F on link B).
 // branch (optional): the smooth piece of the law the point is on: bit 0 = sticking, bits 1.. = face of the primitive
 // (cuboid: 2 axis + (negative side); cylinder: 0 side, 1 / 2 caps; plane, sphere: 0) — see orc_signature.
-template <class T>
-static bool contact_force(int prim, const double* shape, const double* k, const M3<T>& RP, const V3<T>& pP,
-                          const V3<T>& xw, const V3<T>& vrel_w, V3<T>& Fw, int* branch = nullptr) {
+// dd (optional, diagnostics): depth d, normal velocity ddot and tangential speed |vt| of a penetrating point.
+// k = (kn, kt, mu, kd): double from the blob, or Dual seeds over those parameters (parameter adjoint: K = T = Dual).  The branch decisions
+// read the values only, so both instantiations take the same branches.
+template <class T, class K = double>
+static bool contact_force(int prim, const double* shape, const K* k, const M3<T>& RP, const V3<T>& pP,
+                          const V3<T>& xw, const V3<T>& vrel_w, V3<T>& Fw, int* branch = nullptr, double* dd = nullptr) {
   V3<T> x = mulT(RP, xw - pP);
   T d; V3<T> n;
   int face = 0;
@@ -174,8 +177,9 @@ static bool contact_force(int prim, const double* shape, const double* k, const 
   V3<T> F = n * fn;
   double vtn = std::sqrt(val(vt2));
   double fnabs = std::fabs(val(fn));
-  const bool stick = k[1] * vtn <= k[2] * fnabs || vtn < 1e-14;
+  const bool stick = val(k[1]) * vtn <= val(k[2]) * fnabs || vtn < 1e-14;
   if (branch) *branch = (stick ? 1 : 0) | (face << 1);
+  if (dd) { dd[0] = val(d); dd[1] = val(ddot); dd[2] = vtn; }
   if (stick) {
     F = F - vt * T(k[1]);                                  // "sticking": viscous
   } else {
@@ -193,6 +197,10 @@ template <class T> static inline void prim_pose(const Model& m, int pk, const Li
   RP = mul(B.R, cmat<T>(pf + TSIM_PF_R));
   pP = mul(B.R, cvec<T>(pf + TSIM_PF_P)) + B.p;
 }
+
+// Parameter override (parameter adjoint only): Dual seeds for the contact pairs' (kn, kt, mu, kd) [4 npair], the sensors' [4 nsensor] and the
+// dofs' damping [nr]; a null table reads the blob's values as before.
+struct ParamSrc { const Dual* pair = nullptr; const Dual* sensor = nullptr; const Dual* damp = nullptr; };
 
 // ------------------------------------------------------------------------------------------ kinematics + RNEA residual
 template <class T>
@@ -269,8 +277,15 @@ static void kinematics(const Model& m, const T* q, const T* qd, const T* qdd, Li
   }
 }
 
+// the override applies to the Dual instantiations only (a double evaluation never has one)
+template <class T> static inline bool contact_force_p(int, const double*, const Dual*, const M3<T>&, const V3<T>&, const V3<T>&, const V3<T>&, V3<T>&) { abort(); }
+template <> inline bool contact_force_p<Dual>(int prim, const double* shape, const Dual* k, const M3<Dual>& RP, const V3<Dual>& pP, const V3<Dual>& xw,
+                                             const V3<Dual>& vrel, V3<Dual>& Fw) { return contact_force<Dual, Dual>(prim, shape, k, RP, pP, xw, vrel, Fw); }
+template <class T> static inline T damp_p(const Dual&) { abort(); }
+template <> inline Dual damp_p<Dual>(const Dual& d) { return d; }
+
 template <class T>
-static void residual(const Model& m, const T* q, const T* qd, const T* qdd, const T* u, T* r, Link<T>* L) {
+static void residual(const Model& m, const T* q, const T* qd, const T* qdd, const T* u, T* r, Link<T>* L, const ParamSrc* ps = nullptr) {
   V3<T> Ww[MAXR], Wv[MAXR];
   kinematics(m, q, qd, qdd, L, Ww, Wv, true);
   // contacts (dynamics-active pairs)
@@ -288,7 +303,8 @@ static void residual(const Model& m, const T* q, const T* qd, const T* qdd, cons
       }
       V3<T> vrel = (A.v + cross(A.w, xw)) - (Bk.v + cross(Bk.w, xw));
       V3<T> Fw;
-      if (!contact_force<T>(pi[TSIM_PI_PRIM], pf + TSIM_PF_SHAPE, pf + TSIM_PF_KN, RP, pP, xw, vrel, Fw)) continue;
+      if (!(ps && ps->pair ? contact_force_p(pi[TSIM_PI_PRIM], pf + TSIM_PF_SHAPE, ps->pair + 4 * pk, RP, pP, xw, vrel, Fw)
+                           : contact_force<T>(pi[TSIM_PI_PRIM], pf + TSIM_PF_SHAPE, pf + TSIM_PF_KN, RP, pP, xw, vrel, Fw))) continue;
       V3<T> mo = cross(xw, Fw);
       A.ff = A.ff - Fw; A.fn = A.fn - mo;
       if (lb > 0) { Bk.ff = Bk.ff + Fw; Bk.fn = Bk.fn + mo; }
@@ -305,7 +321,7 @@ static void residual(const Model& m, const T* q, const T* qd, const T* qdd, cons
   // joint-space forces: damping, limits, motors
   for (int k = 0; k < m.nr; ++k) {
     const double* df = m.df(k);
-    r[k] = r[k] + qd[k] * T(df[TSIM_DF_DAMPING]);
+    r[k] = r[k] + qd[k] * (ps && ps->damp ? damp_p<T>(ps->damp[k]) : T(df[TSIM_DF_DAMPING]));
     if (df[TSIM_DF_LIM_K] > 0) {
       if (val(q[k]) < df[TSIM_DF_LIM_LO]) r[k] = r[k] - (T(df[TSIM_DF_LIM_LO]) - q[k]) * T(df[TSIM_DF_LIM_K]);
       else if (val(q[k]) > df[TSIM_DF_LIM_HI]) r[k] = r[k] + (q[k] - T(df[TSIM_DF_LIM_HI])) * T(df[TSIM_DF_LIM_K]);
@@ -326,7 +342,7 @@ static void residual(const Model& m, const T* q, const T* qd, const T* qdd, cons
 
 // tactile force vector + end-effector variables at state (q, qd)
 template <class T>
-static void outputs(const Model& m, const T* q, const T* qd, T* var, T* tac, bool want_tac) {
+static void outputs(const Model& m, const T* q, const T* qd, T* var, T* tac, bool want_tac, const ParamSrc* ps = nullptr) {
   Link<T> L[MAXL]; V3<T> Ww[MAXR], Wv[MAXR];
   T zero[MAXR]; for (int k = 0; k < m.nr; ++k) zero[k] = T(0.0);
   kinematics(m, q, qd, zero, L, Ww, Wv, false);
@@ -351,7 +367,8 @@ static void outputs(const Model& m, const T* q, const T* qd, T* var, T* tac, boo
         const Link<T>& Bk = L[pi[TSIM_PI_LINKB]];
         V3<T> vrel = (A.v + cross(A.w, xw)) - (Bk.v + cross(Bk.w, xw));
         V3<T> Fw;
-        if (contact_force<T>(pi[TSIM_PI_PRIM], pf + TSIM_PF_SHAPE, sf, RP[j], pP[j], xw, vrel, Fw)) F = F + Fw;
+        if (ps && ps->sensor ? contact_force_p(pi[TSIM_PI_PRIM], pf + TSIM_PF_SHAPE, ps->sensor + 4 * s, RP[j], pP[j], xw, vrel, Fw)
+                             : contact_force<T>(pi[TSIM_PI_PRIM], pf + TSIM_PF_SHAPE, sf, RP[j], pP[j], xw, vrel, Fw)) F = F + Fw;
       }
       V3<T> Fl = mulT(A.R, F);     // sensor-link frame
       tac[3 * t + 0] = Fl.x * T(m.tax(3, t)) + Fl.y * T(m.tax(4, t)) + Fl.z * T(m.tax(5, t));
@@ -449,6 +466,7 @@ struct Sim {
   int solver = 1;          // 1 (default): LITERAL — exactly what the XML states, and what the HIP kernels run;  0: the round-2 globalisation (legacy, kept to document what it did)
   long newton_iters = 0, substeps = 0, nonconv = 0, evals = 0;
   long kicks = 0, restarts = 0, trust = 0, ls_exhausted = 0;   // how often each globalisation device acted (kernel mode) / a line search ran out (literal mode)
+  double* dLdF = nullptr;  // orc_set_param_grad: table gradient the adjoint adds to (the blob's float records, columns < FOFF_CPT)
 };
 
 // One implicit step in predictor form (covers BDF1 and BDF2):
@@ -655,6 +673,60 @@ static void output_vjp(const Model& m, const double* q0, const double* qd0, cons
   }
 }
 
+// Parameter adjoint of one taped sub-step (orc_set_param_grad): dL/dp += -z^T dg/dp for the dynamics pairs' (kn, kt, mu, kd) and the dofs'
+// damping, g = r / ca at the taped q1 exactly as eval_g_jac_c evaluates it (q1, qd1, qdd1 and u held); forward-mode duals over those columns,
+// NDMAX at a time.  The sensors' parameters do not enter g.
+static void param_vjp_dyn(const Model& m, const double* q1, const StepCoef& c, const double* u, const double* z, double* dLdF) {
+  const int nr = m.nr;
+  std::vector<int> seed;                                            // index into the seed tables: 4 pk + field, or 4 npair + dof
+  for (int pk = 0; pk < m.npair; ++pk) if (m.pi(pk)[TSIM_PI_FLAGS] & 1) for (int f = 0; f < 4; ++f) seed.push_back(4 * pk + f);
+  for (int k = 0; k < nr; ++k) seed.push_back(4 * m.npair + k);
+  std::vector<Dual> kp(std::max(4 * m.npair, 1)), dp(nr);
+  for (int c0 = 0; c0 < (int)seed.size(); c0 += NDMAX) {
+    const int nd = std::min(NDMAX, (int)seed.size() - c0);
+    g_nd = nd;
+    Dual q[MAXR], qd[MAXR], qa[MAXR], uu[MAXR], r[MAXR]; Link<Dual> L[MAXL];
+    for (int k = 0; k < nr; ++k) { double d = q1[k] - c.qpred[k]; q[k] = Dual(q1[k]); qd[k] = Dual(c.qdpred[k] + c.cv * d); qa[k] = Dual(c.ca * d); }
+    for (int j = 0; j < m.nu; ++j) uu[j] = Dual(u[j]);
+    for (int pk = 0; pk < m.npair; ++pk) for (int f = 0; f < 4; ++f) kp[4 * pk + f] = Dual(m.pf(pk)[TSIM_PF_KN + f]);
+    for (int k = 0; k < nr; ++k) dp[k] = Dual(m.df(k)[TSIM_DF_DAMPING]);
+    for (int d = 0; d < nd; ++d) { const int sd = seed[c0 + d]; if (sd < 4 * m.npair) kp[sd].d[d] = 1.0; else dp[sd - 4 * m.npair].d[d] = 1.0; }
+    ParamSrc ps; ps.pair = kp.data(); ps.damp = dp.data();
+    residual<Dual>(m, q, qd, qa, uu, r, L, &ps);
+    for (int d = 0; d < nd; ++d) {
+      double s = 0; for (int i = 0; i < nr; ++i) s += z[i] * r[i].d[d];
+      const int sd = seed[c0 + d];
+      const int col = sd < 4 * m.npair ? m.I[TSIM_IH_FOFF_PAIR] + (sd >> 2) * TSIM_PF_SIZE + TSIM_PF_KN + (sd & 3)
+                                       : m.I[TSIM_IH_FOFF_DOF] + (sd - 4 * m.npair) * TSIM_DF_SIZE + TSIM_DF_DAMPING;
+      dLdF[col] -= s / c.ca;
+    }
+    g_nd = 0;
+  }
+}
+// ... and of a seeded output frame at state (q, qd): dL/dp += wtac^T dtac/dp for the sensors' (kn, kt, mu, kd)
+static void param_vjp_tac(const Model& m, const double* q0, const double* qd0, const double* wtac, double* dLdF) {
+  const int nr = m.nr, ntac3 = 3 * m.ntax, np = 4 * m.nsensor;
+  bool any = false; for (int i = 0; i < ntac3 && wtac; ++i) if (wtac[i] != 0.0) { any = true; break; }
+  if (!any || np == 0) return;
+  std::vector<Dual> var(std::max(3 * m.nvar, 1)), tac(std::max(ntac3, 1)), ks(np);
+  for (int c0 = 0; c0 < np; c0 += NDMAX) {
+    const int nd = std::min(NDMAX, np - c0);
+    g_nd = nd;
+    Dual q[MAXR], qd[MAXR];
+    for (int k = 0; k < nr; ++k) { q[k] = Dual(q0[k]); qd[k] = Dual(qd0[k]); }
+    for (int i = 0; i < np; ++i) ks[i] = Dual(m.sf(i >> 2)[TSIM_SF_KN + (i & 3)]);
+    for (int d = 0; d < nd; ++d) ks[c0 + d].d[d] = 1.0;
+    ParamSrc ps; ps.sensor = ks.data();
+    outputs<Dual>(m, q, qd, var.data(), tac.data(), true, &ps);
+    for (int d = 0; d < nd; ++d) {
+      double s = 0; for (int i = 0; i < ntac3; ++i) s += wtac[i] * tac[i].d[d];
+      const int i = c0 + d;
+      dLdF[m.I[TSIM_IH_FOFF_SENSOR] + (i >> 2) * TSIM_SF_SIZE + TSIM_SF_KN + (i & 3)] += s;
+    }
+    g_nd = 0;
+  }
+}
+
 extern "C" {
 
 void* orc_create(const int* I, const double* F) {
@@ -738,6 +810,10 @@ int orc_backward_steps(void* h, int n, const double* df_dq, const double* df_dva
     if (nu > 0) eval_g_jac_c(m, r.q1.data(), c, r.u.data(), 3, g.data(), Ju.data());
     for (int k = 0; k < nr; ++k) rhs[k] = S.lam_q[k] + c.cv * S.lam_v[k];               // d qd1 / d q1 = cv
     if (!solve_dense(nr, H.data(), rhs.data(), z.data(), true)) return -2;
+    if (S.dLdF) {
+      param_vjp_dyn(m, r.q1.data(), c, r.u.data(), z.data(), S.dLdF);
+      if (df_dtac) param_vjp_tac(m, r.q1.data(), r.qd1.data(), df_dtac + (size_t)j * 3 * m.ntax, S.dLdF);
+    }
     for (int cc = 0; cc < nu; ++cc) { double s = 0; for (int i = 0; i < nr; ++i) s += Ju[i * nu + cc] * z[i]; df_du[j * nu + cc] = -s; }
     std::vector<double> out[4];
     for (int w = 0; w < 4; ++w) {
@@ -762,6 +838,11 @@ int orc_backward_steps(void* h, int n, const double* df_dq, const double* df_dva
   }
   return 0;
 }
+// Table gradient (the oracle's side of tsim_set_param_grad): while dL_dF (the layout of the blob's float records; only the columns the
+// per-environment tables hold, < FOFF_CPT, are touched) is set, orc_backward_steps ADDS dL/d(entry) to it for every contact pair's and tactile
+// sensor's kn kt mu kd and every dof's damping.  nullptr switches it off.
+void orc_set_param_grad(void* h, double* dL_dF) { ((Sim*)h)->dLdF = dL_dF; }
+int orc_table_size(void* h) { return ((Sim*)h)->m.I[TSIM_IH_FOFF_CPT]; }
 void orc_get_adjoint(void* h, double* lam_q, double* lam_v) { Sim& S = *(Sim*)h; for (int k = 0; k < S.m.nr; ++k) { lam_q[k] = S.lam_q[k]; lam_v[k] = S.lam_v[k]; } }
 void orc_clear_adjoint(void* h) { Sim& S = *(Sim*)h; std::fill(S.lam_q.begin(), S.lam_q.end(), 0.0); std::fill(S.lam_v.begin(), S.lam_v.end(), 0.0); std::fill(S.lam_q1.begin(), S.lam_q1.end(), 0.0); std::fill(S.lam_v1.begin(), S.lam_v1.end(), 0.0); }
 
@@ -796,6 +877,35 @@ int orc_contact_list(void* h, const double* q, const double* qd, int max, int* o
         out_i[3 * n] = pk; out_i[3 * n + 1] = i; out_i[3 * n + 2] = br; out_d[2 * n] = d; out_d[2 * n + 1] = med;
       }
       ++n;
+    }
+  }
+  return n;
+}
+
+// diagnostics: the penetrating (taxel, paired primitive) items of the state (q, qd), up to `max` rows of (sensor, taxel index within the sensor,
+// pair, branch): out_i [max][4], out_d [max][3] = (depth d < 0, normal velocity ddot, tangential speed).  Returns the number of such items.
+int orc_taxel_list(void* h, const double* q, const double* qd, int max, int* out_i, double* out_d) {
+  Sim& S = *(Sim*)h; const Model& m = S.m;
+  Link<double> L[MAXL]; V3<double> Ww[MAXR], Wv[MAXR];
+  double zero[MAXR]; for (int k = 0; k < m.nr; ++k) zero[k] = 0.0;
+  kinematics<double>(m, q, qd, zero, L, Ww, Wv, false);
+  int n = 0;
+  for (int s = 0; s < m.nsensor; ++s) {
+    const int* si = m.si(s); const double* sf = m.sf(s);
+    const Link<double>& A = L[si[TSIM_SI_LINK]];
+    for (int j = 0; j < si[TSIM_SI_NSPRIM]; ++j) {
+      int pk = m.sprim(si[TSIM_SI_SPRIM0] + j);
+      const int* pi = m.pi(pk); const double* pf = m.pf(pk);
+      M3<double> RP; V3<double> pP; prim_pose(m, pk, L, RP, pP);
+      const Link<double>& Bk = L[pi[TSIM_PI_LINKB]];
+      for (int i = 0; i < si[TSIM_SI_NTAX]; ++i) {
+        int t = si[TSIM_SI_TAX0] + i;
+        V3<double> xw = mul(A.R, mk<double>(m.tax(0, t), m.tax(1, t), m.tax(2, t))) + A.p;
+        V3<double> vrel = (A.v + cross(A.w, xw)) - (Bk.v + cross(Bk.w, xw)), Fw; int br = 0; double dd[3];
+        if (!contact_force<double>(pi[TSIM_PI_PRIM], pf + TSIM_PF_SHAPE, sf, RP, pP, xw, vrel, Fw, &br, dd)) continue;
+        if (n < max) { out_i[4 * n] = s; out_i[4 * n + 1] = i; out_i[4 * n + 2] = pk; out_i[4 * n + 3] = br; for (int e = 0; e < 3; ++e) out_d[3 * n + e] = dd[e]; }
+        ++n;
+      }
     }
   }
   return n;

@@ -152,35 +152,18 @@ static int push_closed_check(const tsim_batch* b, const tsim_push_policy* pol, i
   if (pol->obs_mean && b->record) return fail(std::string(who) + ": observation normalisation is for roll-out collection (reset with backward_flag = False); the adjoint launch does not undo it");
   return 0;
 }
-#define TS_LAUNCH_POLICY(KERNEL, R, b, km, st, a) do {                                                                               \
-    const LaunchShape L = launch_shape(b);                                                                                           \
-    if constexpr (sizeof(R) == 4) {      /* the statically specialised TactilePush instantiation (tsim_static_pusher.hip) */           \
-      if ((km) == TS_KM_STATIC && L.lpe == 16) { ts_static_pusher_launch_policy(a, L.grid, L.lds, st); break; }                         \
-      if ((km) == TS_KM_PARAM && L.lpe == 16) { ts_param_pusher_launch_policy(a, L.grid, L.lds, st); break; }                           \
-    }                                                                                                                                 \
-    if (L.lpe == 64) hipLaunchKernelGGL((KERNEL<R, 8, false, 64, true>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);                  \
-    else if (L.lpe == 32) hipLaunchKernelGGL((KERNEL<R, 8, false, 32, true>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);             \
-    else hipLaunchKernelGGL((KERNEL<R, 8, false, 16, true>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, a);                              \
-  } while (0)
-
 template <class R>
 static int push_closed_rollout_t(tsim_batch* b, const tsim_push_policy* pol, const void* goal, const void* dist, const void* tac0, int nframes, int nsub,
                                  void* q_out, void* qd_out, void* var_out, void* tac_out, void* u_out, void* gl_out, void* h1_out, void* h2_out, int32_t* status, hipStream_t st) {
-  FwdArgs<R> a;
-  memset(&a, 0, sizeof(a));
-  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.nsub = nsub; a.record = b->record; a.t0 = b->t_cur; a.nframes = nframes; a.tac_slot = nullptr;
-  a.tape = (R*)b->tape; a.u = nullptr;
-  a.q_out = (R*)q_out; a.qd_out = (R*)qd_out; a.var_out = (R*)var_out; a.tac_out = (R*)tac_out; a.status = status; a.evals = b->evals; a.order = nullptr;
-  a.prev = (double*)b->prev; a.has_prev = b->has_prev; a.stage_cpt = b->stage_cpt;
-  a.cross_kinks = b->cross_kinks; a.eval_budget = b->eval_budget; a.gnorm = b->gnorm; a.cull = b->pair_cull; a.vo_ls = b->value_trials;
-  a.default_opts = default_options(b) ? 1 : 0;      // (helpers / value-first trials are off in closed-loop launches whatever the options say: k_forward)
+  FwdArgs<R> a = fwd_args<R>(b);      // (no block order; helpers / value-first trials are off in closed-loop launches whatever the options say: k_forward)
+  a.nsub = nsub; a.nframes = nframes;
+  a.q_out = (R*)q_out; a.qd_out = (R*)qd_out; a.var_out = (R*)var_out; a.tac_out = (R*)tac_out; a.status = status;
   a.pol = make_push_policy<R>(pol);
   a.pol.goal = (const R*)goal; a.pol.dist = (const R*)dist; a.pol.tac0 = (const R*)tac0;
   a.pol.u_out = (R*)u_out; a.pol.gl_out = (R*)gl_out; a.pol.h1_out = (R*)h1_out; a.pol.h2_out = (R*)h2_out;
-  a.tk = b->tape_k;
-  const int km = kernel_mode(b);
-  if (b->record && !launches_fused(b, km, sizeof(R), true)) b->tape_k_ok = 0;      // records without K from here on
-  TS_LAUNCH_POLICY(k_forward, R, b, km, st, a);
+  const TsPlan plan = ts_plan(b, TS_K_FORWARD, true, 0);
+  if (b->record && !plan.fused) b->tape_k_ok = 0;      // records without K from here on
+  if (!ts_launch<true, R>(plan, st, a)) return fail("no closed-loop k_forward instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   b->order_valid = 0; pose_invalidate(b, st);
   return 0;
@@ -206,17 +189,14 @@ template <class R>
 static int push_closed_backward_t(tsim_batch* b, const tsim_push_policy* pol, const void* goal, int nframes, int nsub, const void* df_dq, const void* df_dvar,
                                   const void* du_direct, const void* u_out, const void* h1_out, const void* h2_out, void* g1_out, void* g2_out, void* g3_out,
                                   void* dobs_tac, void* df_du, hipStream_t st) {
-  BwdArgs<R> a;
-  memset(&a, 0, sizeof(a));
-  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.n = nframes * nsub; a.t_end = b->t_cur; a.seed_stride = nsub; a.frames = 1; a.tac_slot = nullptr;
-  a.tape = (const R*)b->tape; a.df_dq = (const R*)df_dq; a.df_dvar = (const R*)df_dvar; a.df_dtac = nullptr;
-  a.lamq = (R*)b->lamq; a.lamv = (R*)b->lamv; a.df_du = (R*)df_du; a.stage_cpt = b->stage_cpt; a.cyc = nullptr; a.cull = b->pair_cull;
+  BwdArgs<R> a = bwd_args<R>(b);
+  a.n = nframes * nsub; a.seed_stride = nsub; a.frames = 1;
+  a.df_dq = (const R*)df_dq; a.df_dvar = (const R*)df_dvar; a.df_du = (R*)df_du;
   a.pol = make_push_policy<R>(pol);
   a.pol.goal = (const R*)goal; a.pol.du_direct = (const R*)du_direct;
   a.pol.u_out = (R*)u_out; a.pol.h1_out = (R*)h1_out; a.pol.h2_out = (R*)h2_out;
   a.pol.g1_out = (R*)g1_out; a.pol.g2_out = (R*)g2_out; a.pol.g3_out = (R*)g3_out; a.pol.dobs_tac = (R*)dobs_tac;
-  a.tk = b->tape_k;
-  TS_LAUNCH_POLICY(k_backward, R, b, b->tape_k_ok ? kernel_mode(b) : TS_KM_GENERIC, st, a);      // the fused adjoint reads K from the tape (launch_backward)
+  if (!ts_launch<true, R>(ts_plan(b, TS_K_BACKWARD, true, 0), st, a)) return fail("no closed-loop k_backward instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -26,6 +26,7 @@
 
 #include "tsim_kernels.h"
 #include "tsim_param_grad.h"
+#include "tsim_launch.h"
 
 // ================================================================================================ LPT ordering
 // One block: counting sort of the environments by their residual-evaluation count of the last launch, descending
@@ -584,7 +585,7 @@ static std::vector<int32_t> build_sched(const std::vector<int32_t>& I, const std
 // the per-point arrays, bit for bit — EXCEPT the taxel layout (number of taxels, a sensor's taxel range and image shape): the static code reads
 // none of it (the read-out kernels and the tactile adjoint take taxels from the batch's own blob), so a TactilePush pad re-gridded to
 // 13 x 13 taxels (BASELINE configs[1]) runs on the same instantiation as the XML's 13 x 10.
-template <class MS> static bool blob_equals_static(const tsim_batch* b) {
+template <class MS> static bool blob_ints_static(const tsim_batch* b) {
   if ((int)b->I.size() != MS::NI || b->I[TSIM_IH_FOFF_CPT] != MS::NFREC) return false;
   auto taxel_layout = [&](int i) {
     if (i == TSIM_IH_NTAXEL || i == TSIM_IH_NF || i == TSIM_IH_NDOF_TACTILE) return true;
@@ -593,6 +594,10 @@ template <class MS> static bool blob_equals_static(const tsim_batch* b) {
     return false;
   };
   for (int i = 0; i < MS::NI; ++i) if (b->I[i] != MS::Iv(i) && !taxel_layout(i)) return false;
+  return true;
+}
+template <class MS> static bool blob_equals_static(const tsim_batch* b) {
+  if (!blob_ints_static<MS>(b)) return false;
   // fp64 batches: the doubles, bit for bit.  fp32 batches: the FLOATS, bit for bit — the fp32 kernels see a model's reals only after their conversion to
   // float (upload_model; ts_F casts the compiled-in constant the same way), so a blob that differs from the asset below float resolution (another host's
   // BLAS in the Python compiler, the native loader of tsim_model.cpp: last bits of mesh-derived mass properties) IS the compiled-in model to them.
@@ -604,14 +609,7 @@ template <class MS> static bool blob_equals_static(const tsim_batch* b) {
 }
 // ... or in its STRUCTURE only: all ints (but the taxel layout) and the structural floats of the compiled asset (TsParam::Fk: exact 0, 1, -1)
 template <class MS> static bool blob_has_structure(const tsim_batch* b) {
-  if ((int)b->I.size() != MS::NI || b->I[TSIM_IH_FOFF_CPT] != MS::NFREC) return false;
-  auto taxel_layout = [&](int i) {
-    if (i == TSIM_IH_NTAXEL || i == TSIM_IH_NF || i == TSIM_IH_NDOF_TACTILE) return true;
-    const int os = MS::Iv(TSIM_IH_OFF_SENSOR), ns = MS::Iv(TSIM_IH_NSENSOR);
-    if (i >= os && i < os + ns * TSIM_SI_SIZE) { const int f = (i - os) % TSIM_SI_SIZE; return f == TSIM_SI_TAX0 || f == TSIM_SI_NTAX || f == TSIM_SI_ROWS || f == TSIM_SI_COLS; }
-    return false;
-  };
-  for (int i = 0; i < MS::NI; ++i) if (b->I[i] != MS::Iv(i) && !taxel_layout(i)) return false;
+  if (!blob_ints_static<MS>(b)) return false;
   for (int i = 0; i < MS::NFREC; ++i) if (MS::Fk(i) && !(b->F[i] == MS::Fv(i))) return false;
   return true;
 }
@@ -619,11 +617,16 @@ static void detect_static_model(tsim_batch* b) {
   b->static_id = blob_has_structure<TsParam<TsStaticPusher>>(b) ? 1 : 0;
   b->static_exact = b->static_id == 1 && blob_equals_static<TsStaticPusher>(b);
 }
-// which instantiation the next launch of the simulation kernels uses: 0 generic, 1 fully static, 2 structure-static (parameters at run time)
-enum { TS_KM_GENERIC = 0, TS_KM_STATIC = 1, TS_KM_PARAM = 2 };
-static int kernel_mode(const tsim_batch* b) {
+// is there an instantiation of the compiled-in model for this kernel at this shape (the batch's precision; tsim_launch.h ts_instantiated)?
+static bool pusher_instantiated(const tsim_batch* b, int kernel, bool policy, bool default_opts, int lpe) {
+  constexpr int nrm = ts_view_nrm<TsStaticPusher>();
+  return ts_instantiated(kernel, nrm, b->dtype == TSIM_F32, policy, default_opts, nrm, false, lpe);
+}
+// the view the batch's model may run on (TS_KM_*, tsim_launch.h), under lanes per environment forced to lpe_forced (0: none): a forced shape
+// the compiled-in model has no instantiation at (fp64 at 16 lanes: its LDS is over the automatic cap) keeps the generic kernels
+static int kernel_mode(const tsim_batch* b, int lpe_forced) {
   if (b->static_id == 0 || b->no_static) return TS_KM_GENERIC;
-  if (b->dtype == TSIM_F64 && b->lpe_forced == 16) return TS_KM_GENERIC;    // fp64: no compiled-in instantiation with four environments per wavefront (16 lanes only when forced: its LDS is over the automatic cap)
+  if (lpe_forced && !pusher_instantiated(b, TS_K_FORWARD, false, false, lpe_forced)) return TS_KM_GENERIC;
   if (b->dFenv) return b->env_struct_ok ? TS_KM_PARAM : TS_KM_GENERIC;      // (the table check is fp32 only: fp64 batches with per-environment tables stay generic)
   return b->static_exact ? TS_KM_STATIC : TS_KM_PARAM;
 }
@@ -720,18 +723,19 @@ static size_t lds_bytes_for(const tsim_batch* b, int nslot) {
 //     rounds x latency(LPE),   rounds = ceil(wavefronts / #SIMDs),   latency(64 : 32 : 16) ~ 1 : 0.93 : 1.02
 // (phase stamps, tools/phase_cycles.py).  The launch takes the LPE that minimises it, subject to the block's LDS
 // leaving room for four blocks per CU.
+// lpe_forced: the shape asked for (0: automatic).
 struct LaunchShape { int lpe; unsigned grid; size_t lds; };
-static LaunchShape launch_shape(const tsim_batch* b) {
+static LaunchShape launch_shape(const tsim_batch* b, int lpe_forced) {
   LaunchShape L;
-  int lpe = b->lpe_forced;
-  const size_t lds_cap = b->lpe_forced ? 64 * 1024 : 40 * 1024;
+  int lpe = lpe_forced;
+  const size_t lds_cap = lpe_forced ? 64 * 1024 : 40 * 1024;
   if (!lpe) {
     lpe = TS_WAVE;
     double best = 1e30;
     const int cand[3] = {64, 32, 16};
     // (the fused static kernels: 1 : 1.13 : 1.24 — their rounds get cheaper with more lanes per environment, so a batch that fills the SIMDs
     // with one environment per wavefront takes that shape: TactilePush 13 x 13 at B = 1024, forward only: 9.0 / 8.0 / 7.3 M env-steps/s)
-    const bool fused_static = kernel_mode(b) != TS_KM_GENERIC;
+    const bool fused_static = kernel_mode(b, 0) != TS_KM_GENERIC;
     const double lat_generic[3] = {1.0, 0.93, 1.02}, lat_static[3] = {1.0, 1.13, 1.24};
     const double* lat = fused_static ? lat_static : lat_generic;
     for (int i = 0; i < 3; ++i) {
@@ -756,57 +760,43 @@ static void decide_stage_cpt(tsim_batch* b) {
   b->stage_cpt = 0;
   if ((size_t)3 * b->I[TSIM_IH_NCPT] * b->esz > TS_CPT_LDS_BYTES) return;
   if (b->dFenv && b->ab_no_envtab_cpt) return;      // A/B: the round-3 behaviour (contact points from global memory next to per-environment tables)
-  const int lpe0 = launch_shape(b).lpe;
+  const int lpe0 = launch_shape(b, b->lpe_forced).lpe;
   b->stage_cpt = 1;
-  if (launch_shape(b).lpe != lpe0 || lds_bytes_for(b, 1) > 64 * 1024) b->stage_cpt = 0;
+  if (launch_shape(b, b->lpe_forced).lpe != lpe0 || lds_bytes_for(b, 1) > 64 * 1024) b->stage_cpt = 0;
 }
-// launchers of the statically specialised instantiations (tsim_static_pusher.hip)
-void ts_static_pusher_launch(const FwdArgs<float>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_static_pusher_launch(const BwdArgs<float>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_static_pusher_launch_policy(const FwdArgs<float>& a, unsigned grid, size_t lds, hipStream_t st);      // ... with the policy between the frames
-void ts_static_pusher_launch_policy(const BwdArgs<float>& a, unsigned grid, size_t lds, hipStream_t st);
-void ts_param_pusher_launch_policy(const FwdArgs<float>& a, unsigned grid, size_t lds, hipStream_t st);       // ... on the structure-static kernels (tsim_param_pusher_policy.hip)
-void ts_param_pusher_launch_policy(const BwdArgs<float>& a, unsigned grid, size_t lds, hipStream_t st);
-void ts_static_pusher_launch_debug(const DbgArgs<float>& a, unsigned grid, size_t lds, hipStream_t st);
-// ... and of the structure-static ones (tsim_param_pusher.hip): the same kernels with the model's parameters read from the float records
-void ts_param_pusher_launch(const FwdArgs<float>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_param_pusher_launch(const BwdArgs<float>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_param_pusher_launch_debug(const DbgArgs<float>& a, unsigned grid, size_t lds, hipStream_t st);
-// ... both in fp64 (two or one environments per wavefront)
-void ts_static_pusher_launch(const FwdArgs<double>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_static_pusher_launch(const BwdArgs<double>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_param_pusher_launch(const FwdArgs<double>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_param_pusher_launch(const BwdArgs<double>& a, int lpe, unsigned grid, size_t lds, hipStream_t st);
-// ... and the SAVEZ twins of their adjoint kernels (tsim_set_param_grad: z of every sub-step saved for the parameter pass)
-void ts_static_pusher_launch(const BwdArgs<float>& a, float* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_static_pusher_launch(const BwdArgs<double>& a, double* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_param_pusher_launch(const BwdArgs<float>& a, float* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_param_pusher_launch(const BwdArgs<double>& a, double* zsave, int lpe, unsigned grid, size_t lds, hipStream_t st);
-// kernel variants: NRM = 8 / 16 rows in the register solve; EXPJ = model has a rotation-vector joint (its code is
-// compiled out otherwise: it costs registers in every evaluation); LPE as above
-// (variadic: the kernel's arguments — k_backward_z, the SAVEZ twin of k_backward, takes the z buffer as a second one)
-#define TS_LAUNCH_L(KERNEL, R, NRM, L, st, ...) do {                                                                     \
-    if (L.lpe == 64) hipLaunchKernelGGL((KERNEL<R, NRM, false, 64>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);         \
-    else if (L.lpe == 32) hipLaunchKernelGGL((KERNEL<R, NRM, false, 32>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);    \
-    else hipLaunchKernelGGL((KERNEL<R, NRM, false, 16>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);                     \
-  } while (0)
-#define TS_LAUNCH(KERNEL, R, b, km, st, ...) do {                                                                        \
-    const LaunchShape L = launch_shape(b);                                                                               \
-    if (sizeof(R) == 4 || L.lpe != 16) {   /* a statically known model (tsim_static.h): instantiated in its own translation unit (fp64: not four environments per wavefront) */ \
-      const int km_ = (km);                                                                                               \
-      if (km_ == TS_KM_STATIC) { ts_static_pusher_launch(__VA_ARGS__, L.lpe, L.grid, L.lds, st); break; }                 \
-      if (km_ == TS_KM_PARAM) { ts_param_pusher_launch(__VA_ARGS__, L.lpe, L.grid, L.lds, st); break; }                   \
-    }                                                                                                                     \
-    if (b->has_exp) hipLaunchKernelGGL((KERNEL<R, 16, true, 64>), dim3(L.grid), dim3(TS_WAVE), L.lds, st, __VA_ARGS__);  \
-    else if (b->nr <= 8) TS_LAUNCH_L(KERNEL, R, 8, L, st, __VA_ARGS__);                                                  \
-    else TS_LAUNCH_L(KERNEL, R, 16, L, st, __VA_ARGS__);                                                                 \
-  } while (0)
-
-// does a simulation launch in kernel mode km run a fused static instantiation (TS_LAUNCH; POLICY: TS_LAUNCH_POLICY, tsim_env_push.h)
-static bool launches_fused(const tsim_batch* b, int km, size_t esz, bool policy) {
-  if (km == TS_KM_GENERIC) return false;
-  const int lpe = launch_shape(b).lpe;
-  return policy ? (esz == 4 && lpe == 16) : (esz == 4 || lpe != 16);
+// ================================================================================================ launch plan
+// Which instantiation of a simulation kernel a launch runs, at which shape — decided here and nowhere else (tsim_launch.h launches the plan).
+// kernel: TS_K_*; policy: the closed loop; lpe: lanes per environment asked for by this launch (0: the batch's, TSIM_LPE /
+// tsim_set_lanes_per_env); the precision is the batch's.  The view is the batch's (kernel_mode) — for the adjoint kernels only on a tape whose
+// K the forward wrote (tape_k_ok: the fused adjoint reads it) — where it has an instantiation (ts_instantiated), else the generic kernels.
+static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
+  int forced = lpe ? lpe : b->lpe_forced;
+  if (kernel == TS_K_DEBUG_EVAL && !forced) forced = TS_WAVE;      // the debug kernel: one environment per wavefront unless a shape is forced
+  const LaunchShape L = launch_shape(b, forced);
+  TsPlan p;
+  p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
+  p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
+  const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z;
+  p.variant = kernel == TS_K_PARAM_GRAD || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
+  p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
+  p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
+  return p;
+}
+// the kernel arguments that come from the batch; each launch sets its own
+template <class R> static FwdArgs<R> fwd_args(const tsim_batch* b) {
+  FwdArgs<R> a{};
+  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.record = b->record; a.t0 = b->t_cur;
+  a.tape = (R*)b->tape; a.evals = b->evals; a.prev = (double*)b->prev; a.has_prev = b->has_prev; a.stage_cpt = b->stage_cpt;
+  a.cross_kinks = b->cross_kinks; a.eval_budget = b->eval_budget; a.gnorm = b->gnorm; a.cull = b->pair_cull; a.vo_ls = b->value_trials;
+  a.default_opts = default_options(b) ? 1 : 0; a.tk = b->tape_k;
+  return a;
+}
+template <class R> static BwdArgs<R> bwd_args(const tsim_batch* b) {
+  BwdArgs<R> a{};
+  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.t_end = b->t_cur;
+  a.tape = (const R*)b->tape; a.lamq = (R*)b->lamq; a.lamv = (R*)b->lamv; a.stage_cpt = b->stage_cpt; a.cull = b->pair_cull; a.tk = b->tape_k;
+  return a;
 }
 
 // Pads too large for the in-kernel read-out (lanes of one environment over its taxels) are read on demand by tsim_readout; for those
@@ -852,12 +842,11 @@ static int launch_taxels(tsim_batch* b, const void* poseR, const double* poseD, 
 
 template <class R>
 static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32_t* tac_slot, int nsub, void* q_out, void* qd_out, void* var_out, void* tac_out, int32_t* status, hipStream_t st) {
-  FwdArgs<R> a;
-  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.nsub = nsub; a.record = b->record; a.t0 = b->t_cur; a.nframes = nframes; a.tac_slot = tac_slot;
-  a.tape = (R*)b->tape; a.u = (const R*)u;
-  a.q_out = (R*)q_out; a.qd_out = (R*)qd_out; a.var_out = (R*)var_out; a.tac_out = (R*)tac_out; a.status = status; a.evals = b->evals; a.order = (b->B >= 256 && nframes == 1 && b->order_valid) ? b->order : (b->B >= 256 && nframes > 1 && b->order_ep_n == nframes * nsub && !b->ab_no_episode_lpt) ? b->order_ep : nullptr;
-  a.prev = (double*)b->prev; a.has_prev = b->has_prev; a.stage_cpt = b->stage_cpt;
-  a.cross_kinks = b->cross_kinks; a.eval_budget = b->eval_budget; a.gnorm = b->gnorm; a.cull = b->pair_cull; a.vo_ls = b->value_trials; a.vo_first = b->value_first; a.helpers = b->trial_helpers; a.helped = b->helped;
+  FwdArgs<R> a = fwd_args<R>(b);
+  a.nsub = nsub; a.nframes = nframes; a.tac_slot = tac_slot; a.u = (const R*)u;
+  a.q_out = (R*)q_out; a.qd_out = (R*)qd_out; a.var_out = (R*)var_out; a.tac_out = (R*)tac_out; a.status = status;
+  a.order = (b->B >= 256 && nframes == 1 && b->order_valid) ? b->order : (b->B >= 256 && nframes > 1 && b->order_ep_n == nframes * nsub && !b->ab_no_episode_lpt) ? b->order_ep : nullptr;
+  a.vo_first = b->value_first; a.helpers = b->trial_helpers; a.helped = b->helped;
   const bool emit = pose_emit(b, st);
   a.nspt = b->nspt;
   if (emit) { a.poseR = (R*)b->poseR; a.poseD = b->poseD; }
@@ -887,16 +876,14 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   a.free_run = (defer || !tac_out || b->ntax == 0) && !b->ab_no_free_run;
   a.lockstep = b->ab_lockstep ? 1 : 0;
   if (a.lockstep) a.free_run = 0;
-  a.default_opts = default_options(b) ? 1 : 0;
-  a.tk = b->tape_k;
-  const int km = kernel_mode(b);
-  if (b->record && !launches_fused(b, km, sizeof(R), false)) b->tape_k_ok = 0;      // records without K from here on
-  { KtScope kt_(b, TSIM_KT_FORWARD, st); TS_LAUNCH(k_forward, R, b, km, st, a); }
+  const TsPlan plan = ts_plan(b, TS_K_FORWARD, false, 0);
+  if (b->record && !plan.fused) b->tape_k_ok = 0;      // records without K from here on
+  { KtScope kt_(b, TSIM_KT_FORWARD, st); if (!ts_launch<false, R>(plan, st, a)) return fail("no k_forward instantiation for the launch plan"); }
   HIPCHK(hipGetLastError());
   if (defer) { KtScope kt_(b, TSIM_KT_TAXELS, st); if (launch_taxels<R>(b, b->fposeR, b->fposeD, nframes, tac_slot, tac_out, st)) return 1; }
   b->pose_valid = emit ? 1 : 0;
   if (b->B >= 256) {
-    const int ns = TS_WAVE / launch_shape(b).lpe, nsv = (b->B % ns == 0) ? ns : 1;
+    const int ns = TS_WAVE / plan.lpe, nsv = (b->B % ns == 0) ? ns : 1;
     if (nframes > 1) {          // episode totals: the order of the next episode launch of this length (kept across resets)
       const int n = nframes * nsub;
       hipLaunchKernelGGL(k_order_by_evals, dim3(1), dim3(1024), 0, st, (const int*)b->evals, b->order_ep, b->B, nsv, 2 * n, std::max(1, 5 * n / 2), b->ab_lpt_deal);
@@ -928,10 +915,9 @@ static int launch_param_grad(tsim_batch* b, int n, int seed_stride, int frames, 
   p.nchunk = (n + p.chunk_len - 1) / p.chunk_len;          // (no empty chunk)
   p.P = ts_pg_count(npair, nsensor, b->nr); p.part = (R*)b->pgpart; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
   if (p.nchunk > b->pg_chunks) return fail("param_grad: partial-sum buffer too small");
-  const LaunchShape L = launch_shape(b);
-  const int ns = TS_WAVE / (b->has_exp ? TS_WAVE : L.lpe);
-  const unsigned grid = (unsigned)(p.nchunk * ((b->B + ns - 1) / ns));
-  ts_param_grad_launch(p, b->has_exp != 0, b->has_exp ? TS_WAVE : L.lpe, grid, lds_bytes_for(b, ns), st);
+  TsPlan plan = ts_plan(b, TS_K_PARAM_GRAD, false, 0);
+  plan.grid *= p.nchunk;
+  if (!TsLaunch<void, false, R>::run(plan, st, p)) return fail("no k_param_grad instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   PgReduceArgs<R> r{(const R*)b->pgpart, p.nchunk, b->B, p.P, (R*)b->dLdp, b->nfrec, npair, nsensor, b->nr,
                     b->I[TSIM_IH_FOFF_PAIR], b->I[TSIM_IH_FOFF_SENSOR], b->I[TSIM_IH_FOFF_DOF]};
@@ -942,19 +928,15 @@ static int launch_param_grad(tsim_batch* b, int n, int seed_stride, int frames, 
 
 template <class R>
 static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, const int32_t* tac_slot, const void* df_dq, const void* df_dvar, const void* df_dtac, void* df_du, hipStream_t st) {
-  BwdArgs<R> a;
-  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.n = n; a.t_end = b->t_cur; a.seed_stride = seed_stride; a.frames = frames; a.tac_slot = tac_slot;
-  a.tape = (const R*)b->tape; a.df_dq = (const R*)df_dq; a.df_dvar = (const R*)df_dvar; a.df_dtac = (const R*)df_dtac;
-  a.lamq = (R*)b->lamq; a.lamv = (R*)b->lamv; a.df_du = (R*)df_du; a.stage_cpt = b->stage_cpt; a.cyc = b->bwd_stamps; a.cull = b->pair_cull;
-  a.tk = b->tape_k;
+  BwdArgs<R> a = bwd_args<R>(b);
+  a.n = n; a.seed_stride = seed_stride; a.frames = frames; a.tac_slot = tac_slot;
+  a.df_dq = (const R*)df_dq; a.df_dvar = (const R*)df_dvar; a.df_dtac = (const R*)df_dtac; a.df_du = (R*)df_du; a.cyc = b->bwd_stamps;
   {
     KtScope kt_(b, TSIM_KT_BACKWARD, st);
-    const int keep_ = b->lpe_forced;
-    if (b->ab_bwd_lpe) b->lpe_forced = b->ab_bwd_lpe;      // A/B (TSIM_BWD_LPE at creation): another launch shape for the adjoint kernel (the tape does not depend on it)
-    const int km = b->tape_k_ok ? kernel_mode(b) : TS_KM_GENERIC;      // the fused adjoint reads K from the tape: only where the forward wrote it
-    if (b->dLdp) TS_LAUNCH(k_backward_z, R, b, km, st, a, (R*)b->zbuf);      // the same variant's SAVEZ twin: z of every sub-step for the parameter pass
-    else TS_LAUNCH(k_backward, R, b, km, st, a);
-    b->lpe_forced = keep_;
+    // with the parameter pass: the same variant's SAVEZ twin (z of every sub-step).  TSIM_BWD_LPE at creation (A/B): another launch shape for
+    // the adjoint kernel (the tape does not depend on it)
+    const TsPlan plan = ts_plan(b, b->dLdp ? TS_K_BACKWARD_Z : TS_K_BACKWARD, false, b->ab_bwd_lpe);
+    if (!ts_launch<false, R>(plan, st, a, (R*)b->zbuf)) return fail("no k_backward instantiation for the launch plan");
   }
   HIPCHK(hipGetLastError());
   if (b->dLdp) return launch_param_grad<R>(b, n, seed_stride, frames, tac_slot, df_dtac, st);
@@ -1012,7 +994,7 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   }
   b->stage_cpt = 0;
   detect_static_model(b);      // before the staging decision: the launch shape depends on which kernels run
-  b->tape_k = kernel_mode(b) != TS_KM_GENERIC ? 1 : 0;
+  b->tape_k = kernel_mode(b, b->lpe_forced) != TS_KM_GENERIC ? 1 : 0;
   b->rec = ts_rec(nr, nu, (int)b->esz, b->tape_k);
   if (lds_bytes_for(b, 1) > 64 * 1024) { delete b; return fail("model needs more than 64 KiB of LDS per environment"); }
   decide_stage_cpt(b);
@@ -1054,7 +1036,7 @@ int tsim_dtype(const tsim_batch* b) { return b->dtype; }
 double tsim_timestep(const tsim_batch* b) { return b->F[TSIM_FH_H]; }
 int tsim_tape_len(const tsim_batch* b) { return b->record ? b->t_cur : 0; }
 int tsim_launch_info(const tsim_batch* b, int32_t* out) {
-  const LaunchShape L = launch_shape(b);
+  const LaunchShape L = launch_shape(b, b->lpe_forced);
   out[0] = (int32_t)L.lds; out[1] = TS_WAVE; out[2] = (int32_t)L.grid; out[3] = L.lpe;
   return 0;
 }
@@ -1080,9 +1062,9 @@ int tsim_set_lanes_per_env(tsim_batch* b, int lanes) {
   decide_stage_cpt(b);      // depends on the shape; the flag travels with every launch as a kernel argument: nothing on the device to update
   return 0;
 }
-int tsim_static_model(const tsim_batch* b) { return kernel_mode(b) != TS_KM_GENERIC ? b->static_id : 0; }
+int tsim_static_model(const tsim_batch* b) { return kernel_mode(b, b->lpe_forced) != TS_KM_GENERIC ? b->static_id : 0; }
 const char* tsim_kernel_variant(const tsim_batch* b) {
-  const int km = kernel_mode(b);
+  const int km = kernel_mode(b, b->lpe_forced);
   if (km == TS_KM_STATIC) return "static:pusher";
   if (km == TS_KM_PARAM) return "param:pusher";
   return "generic";
@@ -1405,25 +1387,17 @@ int tsim_debug_stamps(tsim_batch* b, long long* cycles) { b->bwd_stamps = cycles
 
 int tsim_debug_eval(tsim_batch* b, const void* q1, const void* q0, const void* qd0, const void* u, void* g_out, void* H_out, long long* cycles, void* stream) {
   TS_DEVICE(b);
-  // one environment per wavefront, unless TSIM_LPE forces a packed shape (nr <= 8 models: the stamped variant is NRM 8) — the shape the steps
-  // take, wider where the forced one's LDS does not fit (launch_shape)
-  const int lpe = (b->lpe_forced && !b->has_exp && (!cycles || b->nr <= 8)) ? launch_shape(b).lpe : TS_WAVE;
-  const int ns = TS_WAVE / lpe;
-  const dim3 grid((b->B + ns - 1) / ns), blk(TS_WAVE);
-  const size_t lds = lds_bytes_for(b, ns);
+  // the stamped variant of an nr > 8 model: one environment per wavefront whatever the batch's shape (ts_plan: the debug kernel's shape)
+  const TsPlan plan = ts_plan(b, TS_K_DEBUG_EVAL, false, cycles && b->nr > 8 ? TS_WAVE : 0);
+  bool ok;
   if (b->dtype == TSIM_F32) {
     DbgArgs<float> a{b->dI, (const float*)b->dF, (const float*)b->dFenv, b->nfrec, b->B, (const float*)q1, (const float*)q0, (const float*)qd0, (const float*)u, (float*)g_out, (float*)H_out, cycles, b->stage_cpt, b->pair_cull};
-    if (lpe == 16 && kernel_mode(b) == TS_KM_STATIC) ts_static_pusher_launch_debug(a, grid.x, lds, (hipStream_t)stream);      // the static sweep's g and H
-    else if (lpe == 16 && kernel_mode(b) == TS_KM_PARAM) ts_param_pusher_launch_debug(a, grid.x, lds, (hipStream_t)stream);
-    else if (lpe == 16) hipLaunchKernelGGL((k_debug_eval<float, 16>), grid, blk, lds, (hipStream_t)stream, a);
-    else if (lpe == 32) hipLaunchKernelGGL((k_debug_eval<float, 32>), grid, blk, lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_debug_eval<float, 64>), grid, blk, lds, (hipStream_t)stream, a);
+    ok = ts_launch<false, float>(plan, (hipStream_t)stream, a);
   } else {
     DbgArgs<double> a{b->dI, (const double*)b->dF, (const double*)b->dFenv, b->nfrec, b->B, (const double*)q1, (const double*)q0, (const double*)qd0, (const double*)u, (double*)g_out, (double*)H_out, cycles, b->stage_cpt, b->pair_cull};
-    if (lpe == 16) hipLaunchKernelGGL((k_debug_eval<double, 16>), grid, blk, lds, (hipStream_t)stream, a);
-    else if (lpe == 32) hipLaunchKernelGGL((k_debug_eval<double, 32>), grid, blk, lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_debug_eval<double, 64>), grid, blk, lds, (hipStream_t)stream, a);
+    ok = ts_launch<false, double>(plan, (hipStream_t)stream, a);
   }
+  if (!ok) return fail("no k_debug_eval instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -1,0 +1,107 @@
+// tsim_launch.h — launch plans of the simulation kernels and the one launcher that runs them.
+//
+// A plan (TsPlan, made by tsim_hip.hip ts_plan and nowhere else) names one instantiation of k_forward, k_backward, k_backward_z, k_debug_eval
+// or k_param_grad and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
+// (tsim_hip.hip; k_param_grad: tsim_param_grad.hip), or a compiled-in model (tsim_static.h), whose translation units hold nothing but the
+// explicit instantiations of TsLaunch for their view: they are built with flags of their own (host/buildhash.py HIP_UNITS).
+#pragma once
+#include <type_traits>
+#include "tsim_kernels.h"
+#include "tsim_param_grad.h"
+#include "tsim_static_pusher.h"
+
+enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD };
+// the view of a launch: the generic kernels, a compiled-in model fully static, or its structure-static twin (parameters at run time)
+enum { TS_KM_GENERIC = 0, TS_KM_STATIC = 1, TS_KM_PARAM = 2 };
+using TsParamPusher = TsParam<TsStaticPusher>;
+
+struct TsPlan {
+  int kernel = TS_K_FORWARD, variant = TS_KM_GENERIC;
+  int nrm = 8; bool expj = false; int lpe = TS_WAVE;      // rows of the register solve, rotation-vector joint compiled in, lanes per environment
+  bool policy = false;                                    // the TactilePush policy between the frames (tsim_policy_push.h)
+  bool default_opts = false;                              // every option at its default: the TsDefaultOpts<> instantiation (tsim_static.h)
+  unsigned grid = 0; size_t lds = 0;
+  bool fused = false;      // the view's model is FUSED (ts_static_fused): its forward writes K next to H on the tape, its adjoint reads it
+};
+
+// NRM of a view: 0 for the generic kernels (any), else the compiled-in model's
+template <class MS> constexpr int ts_view_nrm() { return ts_static_nr<MS>() == 0 ? 0 : (ts_static_nr<MS>() <= 8 ? 8 : 16); }
+
+// The instantiations there are, in one list: ts_plan runs the generic kernels where a compiled-in model has none, TsLaunch compiles exactly these
+// (tests/test_capi_symbols.py pins the set).  Every view: NRM 8 / 16 at 16 / 32 / 64 lanes per environment, a rotation-vector joint only at NRM 16
+// and 64 lanes; the closed loop: TactilePush's forward and adjoint (NRM 8).  A compiled-in model (ms_nrm != 0): its own NRM, no parameter pass;
+// fp64 not at 16 lanes (four environments' LDS is over the cap); the closed loop and the debug kernel at fp32 and 16 lanes only; the TsDefaultOpts<>
+// twin of the forward kernel at fp32 and 16 lanes.
+constexpr bool ts_instantiated(int kernel, int ms_nrm, bool fp32, bool policy, bool default_opts, int nrm, bool expj, int lpe) {
+  if ((expj && (nrm != 16 || lpe != 64)) || (nrm != 8 && nrm != 16) || (lpe != 16 && lpe != 32 && lpe != 64)) return false;
+  if (policy && (nrm != 8 || expj || (kernel != TS_K_FORWARD && kernel != TS_K_BACKWARD))) return false;
+  if (ms_nrm == 0) return !default_opts;
+  if (kernel == TS_K_PARAM_GRAD || nrm != ms_nrm || expj) return false;
+  if (default_opts) return kernel == TS_K_FORWARD && fp32 && lpe == 16;
+  if (policy || kernel == TS_K_DEBUG_EVAL) return fp32 && lpe == 16;
+  return fp32 || lpe != 16;
+}
+
+template <class R, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_param_grad(PgArgs<R> a);      // tsim_param_grad.hip
+
+template <int N> using TsInt = std::integral_constant<int, N>;
+template <bool B> using TsBool = std::integral_constant<bool, B>;
+
+// run(): the launch of the instantiation plan p names, in view MS (void: generic) with the policy or without; false where there is none (the
+// plan is for another view or kernel).  The members are defined out of the class, not inline, so that `extern template` below keeps a
+// compiled-in view's kernels out of every unit but its own.
+template <class MS, bool POLICY, class R> struct TsLaunch {
+  // f(NRM, EXPJ, LPE) as constants for the plan's shape, instantiated only where ts_instantiated lists the instantiation
+  template <int K, class F> static bool shape(const TsPlan& p, F&& f) {
+    if (p.kernel != K || p.policy != POLICY) return false;
+    auto at = [&](auto nrm, auto expj, auto lpe) {
+      if constexpr (ts_instantiated(K, ts_view_nrm<MS>(), sizeof(R) == 4, POLICY, false, nrm, expj, lpe)) { f(nrm, expj, lpe); return true; }
+      else return false;
+    };
+    auto lanes = [&](auto nrm, auto expj) { return p.lpe == 16 ? at(nrm, expj, TsInt<16>()) : p.lpe == 32 ? at(nrm, expj, TsInt<32>()) : p.lpe == 64 && at(nrm, expj, TsInt<64>()); };
+    if (p.expj) return p.nrm == 16 && lanes(TsInt<16>(), TsBool<true>());
+    return p.nrm == 8 ? lanes(TsInt<8>(), TsBool<false>()) : p.nrm == 16 && lanes(TsInt<16>(), TsBool<false>());
+  }
+  static bool run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a);
+  static bool run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave = nullptr);      // zsave: k_backward_z (TS_K_BACKWARD_Z)
+  static bool run(const TsPlan& p, hipStream_t st, const DbgArgs<R>& a);
+  static bool run(const TsPlan& p, hipStream_t st, const PgArgs<R>& a);
+};
+
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a) {
+  return shape<TS_K_FORWARD>(p, [&](auto nrm, auto expj, auto lpe) {
+    if constexpr (ts_instantiated(TS_K_FORWARD, ts_view_nrm<MS>(), sizeof(R) == 4, POLICY, true, nrm, expj, lpe)) {
+      if (p.default_opts) { hipLaunchKernelGGL((k_forward<R, nrm, expj, lpe, POLICY, TsDefaultOpts<MS>>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); return; }
+    }
+    hipLaunchKernelGGL((k_forward<R, nrm, expj, lpe, POLICY, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a);
+  });
+}
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave) {
+  if (p.kernel == TS_K_BACKWARD_Z)
+    return shape<TS_K_BACKWARD_Z>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_backward_z<R, nrm, expj, lpe, POLICY, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a, zsave); });
+  return shape<TS_K_BACKWARD>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_backward<R, nrm, expj, lpe, POLICY, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
+}
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const DbgArgs<R>& a) {
+  return shape<TS_K_DEBUG_EVAL>(p, [&](auto, auto, auto lpe) { hipLaunchKernelGGL((k_debug_eval<R, lpe, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
+}
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const PgArgs<R>& a) {
+  return shape<TS_K_PARAM_GRAD>(p, [&](auto, auto expj, auto lpe) { hipLaunchKernelGGL((k_param_grad<R, expj, lpe>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
+}
+
+// ... in the plan's view
+template <bool POLICY, class R, class A, class... Z> bool ts_launch(const TsPlan& p, hipStream_t st, const A& a, Z... z) {
+  if (p.variant == TS_KM_STATIC) return TsLaunch<TsStaticPusher, POLICY, R>::run(p, st, a, z...);
+  if (p.variant == TS_KM_PARAM) return TsLaunch<TsParamPusher, POLICY, R>::run(p, st, a, z...);
+  return TsLaunch<void, POLICY, R>::run(p, st, a, z...);
+}
+// instantiated in their own units: tsim_static_pusher.hip, tsim_param_pusher.hip, their _policy twins, tsim_param_grad.hip
+extern template struct TsLaunch<TsStaticPusher, false, float>;
+extern template struct TsLaunch<TsStaticPusher, false, double>;
+extern template struct TsLaunch<TsStaticPusher, true, float>;
+extern template struct TsLaunch<TsStaticPusher, true, double>;
+extern template struct TsLaunch<TsParamPusher, false, float>;
+extern template struct TsLaunch<TsParamPusher, false, double>;
+extern template struct TsLaunch<TsParamPusher, true, float>;
+extern template struct TsLaunch<TsParamPusher, true, double>;
+extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const PgArgs<float>&);
+extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PgArgs<double>&);

@@ -1,4 +1,4 @@
-// tsim_param_grad.h — arguments and launchers of the parameter-gradient pass (csrc/tsim_param_grad.hip; include/tsim.h tsim_set_param_grad).
+// tsim_param_grad.h — arguments of the parameter-gradient pass (csrc/tsim_param_grad.hip; include/tsim.h tsim_set_param_grad; its launch: tsim_launch.h).
 //
 // What it adds, per environment, for the physical parameters of the numeric tables (DESIGN.md §4 "Parameter gradient"):
 //     dL/dp = sum_t -(dg_t/dp)^T z_t  +  sum_{seeded frames} (dtactile/dp)^T w_tac
@@ -29,7 +29,5 @@ template <class R> struct PgReduceArgs {
   int npair, nsensor, nr, foff_pair, foff_sensor, foff_dof;
 };
 
-void ts_param_grad_launch(const PgArgs<float>& a, bool expj, int lpe, unsigned grid, size_t lds, hipStream_t st);
-void ts_param_grad_launch(const PgArgs<double>& a, bool expj, int lpe, unsigned grid, size_t lds, hipStream_t st);
 void ts_param_reduce_launch(const PgReduceArgs<float>& a, hipStream_t st);
 void ts_param_reduce_launch(const PgReduceArgs<double>& a, hipStream_t st);

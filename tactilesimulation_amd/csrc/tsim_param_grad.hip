@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "tsim_kernels.h"
 #include "tsim_param_grad.h"
+#include "tsim_launch.h"
 
 // Adds v[k] to out[i0 + k], k < 4.  Entry i of a slot's partial row is always touched by lane i % LPE of the slot — zeroing included — so every
 // read-modify-write sees its own earlier stores (program order of one lane; no cross-lane ordering is relied on).
@@ -167,15 +168,9 @@ __global__ void __launch_bounds__(256) k_param_reduce(PgReduceArgs<R> a) {
   a.out[(size_t)env * a.stride + col] += s;
 }
 
-template <class R>
-static void pg_launch(const PgArgs<R>& a, bool expj, int lpe, unsigned grid, size_t lds, hipStream_t st) {
-  if (expj) hipLaunchKernelGGL((k_param_grad<R, true, 64>), dim3(grid), dim3(TS_WAVE), lds, st, a);
-  else if (lpe == 64) hipLaunchKernelGGL((k_param_grad<R, false, 64>), dim3(grid), dim3(TS_WAVE), lds, st, a);
-  else if (lpe == 32) hipLaunchKernelGGL((k_param_grad<R, false, 32>), dim3(grid), dim3(TS_WAVE), lds, st, a);
-  else hipLaunchKernelGGL((k_param_grad<R, false, 16>), dim3(grid), dim3(TS_WAVE), lds, st, a);
-}
-void ts_param_grad_launch(const PgArgs<float>& a, bool expj, int lpe, unsigned grid, size_t lds, hipStream_t st) { pg_launch(a, expj, lpe, grid, lds, st); }
-void ts_param_grad_launch(const PgArgs<double>& a, bool expj, int lpe, unsigned grid, size_t lds, hipStream_t st) { pg_launch(a, expj, lpe, grid, lds, st); }
+// the launch itself: tsim_launch.h, as every simulation kernel's (the plan: tsim_hip.hip launch_param_grad)
+template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const PgArgs<float>&);
+template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PgArgs<double>&);
 void ts_param_reduce_launch(const PgReduceArgs<float>& a, hipStream_t st) {
   hipLaunchKernelGGL(k_param_reduce<float>, dim3((unsigned)((a.B * a.P + 255) / 256)), dim3(256), 0, st, a);
 }

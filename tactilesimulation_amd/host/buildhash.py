@@ -140,7 +140,7 @@ def write_kernel_table(lib=None, out=None):
 
 
 def kernel_name(kernel, dtype, nr, has_exp, lanes, variant, policy=False, default_opts=False):
-    """Mangled name of the instantiation of k_forward / k_backward a batch launches (csrc/tsim_hip.hip TS_LAUNCH) and a readable form of it.
+    """Mangled name of the instantiation of k_forward / k_backward a batch launches (csrc/tsim_hip.hip ts_plan) and a readable form of it.
     default_opts: every solver / scheduling option of the batch is at its default (tsim_get_option TSIM_OPT_ALL_DEFAULT): the fp32 forward launch of a
     compiled-in model at 16 lanes per environment then runs the TsDefaultOpts<> instantiation (csrc/tsim_static.h)."""
     nrm, expj, lpe = (16, True, 64) if has_exp else ((8 if nr <= 8 else 16), False, lanes)

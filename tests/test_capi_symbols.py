@@ -74,6 +74,33 @@ def test_kernel_table_names_the_instantiations_a_batch_launches():
         assert mangled in table, (readable, mangled)
         rec = table[mangled]
         assert rec["vgpr_count"] > 0 and rec["code_bytes"] > 0 and rec["max_flat_workgroup_size"] == 64, (readable, rec)
+    # ... and nothing more: the instantiations of the four simulation kernels are exactly these (csrc/tsim_launch.h ts_instantiated), so a
+    # dispatcher cannot add one unnoticed.  (kernel, real, NRM, EXPJ, LPE, POLICY, view); the debug kernel has no NRM / EXPJ / POLICY
+    import re
+    views = {"v": "generic", "14TsStaticPusher": "static:pusher", "7TsParamI14TsStaticPusherE": "param:pusher",
+             "13TsDefaultOptsI14TsStaticPusherE": "static:pusher+default_opts", "13TsDefaultOptsI7TsParamI14TsStaticPusherEE": "param:pusher+default_opts"}
+    got = set()
+    for name in table:
+        if not re.match(r"_Z\d+(k_forward|k_backward|k_backward_z|k_debug_eval)I", name):
+            continue
+        m = re.match(r"_Z\d+(k_forward|k_backward|k_backward_z)I([fd])Li(\d+)ELb([01])ELi(\d+)ELb([01])E(.+?)Ev7[FB]wdArgs", name)
+        d = re.match(r"_Z\d+k_debug_evalI([fd])Li(\d+)E(.+?)Ev7DbgArgs", name)
+        assert (m or d) and (m or d).groups()[-1] in views, name
+        got.add((m[1], m[2], int(m[3]), m[4] == "1", int(m[5]), m[6] == "1", views[m[7]]) if m else ("k_debug_eval", d[1], None, False, int(d[2]), False, views[d[3]]))
+    want = set()
+    shapes = [(n, False, l) for n in (8, 16) for l in (16, 32, 64)] + [(16, True, 64)]
+    for dt in "fd":
+        want |= {(k, dt, n, x, l, False, "generic") for k in ("k_forward", "k_backward", "k_backward_z") for n, x, l in shapes}
+        want |= {(k, dt, 8, False, l, True, "generic") for k in ("k_forward", "k_backward") for l in (16, 32, 64)}      # closed loop
+        want |= {("k_debug_eval", dt, None, False, l, False, "generic") for l in (16, 32, 64)}
+    for v in ("static:pusher", "param:pusher"):
+        want |= {(k, "f", 8, False, l, False, v) for k in ("k_forward", "k_backward", "k_backward_z") for l in (16, 32, 64)}
+        want |= {(k, "d", 8, False, l, False, v) for k in ("k_forward", "k_backward", "k_backward_z") for l in (32, 64)}
+        want |= {(k, "f", 8, False, 16, True, v) for k in ("k_forward", "k_backward")}
+        want |= {("k_forward", "f", 8, False, 16, pol, v + "+default_opts") for pol in (False, True)}
+        want.add(("k_debug_eval", "f", None, False, 16, False, v))
+    assert len(want) == 100
+    assert got == want, ("not listed", sorted(got - want, key=str), "missing", sorted(want - got, key=str))
 
 
 def test_public_headers_are_plain_c99_and_cxx17(tmp_path):

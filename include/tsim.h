@@ -73,6 +73,24 @@ int tsim_table_size(const tsim_batch* b);
  * closed-loop launches (tsim_push_closed_backward fails while it is set). */
 int tsim_set_param_grad(tsim_batch* b, void* dL_dtables);
 
+/* Which groups of table entries tsim_set_param_grad's buffer receives (a mask of TSIM_PG_*; the default, TSIM_PG_CONTACT, is the list above):
+ *   TSIM_PG_INERTIAL  per link: mass, centre of mass (3, link frame), inertia about it (6: xx yy zz xy xz yz, link frame) — TSIM_TAB_LINK.
+ *                     g_j contains W_j . sum_{i in subtree(j)} F_i / ca, F_i = I_i A_i + V_i x* I_i V_i the link's inertial wrench (gravity is the
+ *                     world's acceleration), so the term is -(Z_i . dF_i/dp) / ca with Z_i = sum_{j above i} z_j W_j; the sub-step's discrete
+ *                     accelerations are those of the adjoint.  Massless intermediate links of a free3d-* joint get their derivative too.
+ *   TSIM_PG_MOTOR     per entry of u: lo hi P D — TSIM_TAB_MOTOR.  Force control: d tau/d lo = 1 - s, d tau/d hi = s, s = (clip(u, -1, 1) + 1) / 2,
+ *                     P and D exactly 0; position control: d tau/d P = u - q, d tau/d D = -qd, lo and hi exactly 0.
+ *   TSIM_PG_LIMIT     per dof: lim_lo lim_hi lim_k — TSIM_TAB_LIMIT; the one-sided derivative of the piece the state is on, exactly 0 inside
+ *                     the limits and for a dof without a limit (lim_k == 0).
+ * Host-side only; takes effect with the next adjoint launch.  With the default mask nothing more is launched or allocated and every result is
+ * bit-identical; a body group adds one pass over (environment, chunk of sub-steps) and its fixed-order reduction (csrc/tsim_param_grad_body.hip
+ * k_param_grad_body).  Without TSIM_PG_CONTACT the contact, tactile and damping columns are left untouched.
+ * Not differentiated, by design: geometry (joint frames and axes, primitive frames and shapes, contact points, taxels, end-effector
+ * positions), the float header (time step, gravity, tolerance), and the B = 1 redmax_py shim's flag_p. */
+enum { TSIM_PG_CONTACT = 1, TSIM_PG_INERTIAL = 2, TSIM_PG_MOTOR = 4, TSIM_PG_LIMIT = 8 };
+int tsim_set_param_grad_groups(tsim_batch* b, int mask);
+int tsim_get_param_grad_groups(const tsim_batch* b);      /* the mask (-1: null batch) */
+
 /* sim.set_state_init(q, qdot) + sim.reset(backward_flag)      envs/redmax_torch_functions.py:39-41,
  * envs/tactile_push_env.py:138,154.  q0 / qd0: [B][ndof_r].  Restarts the tape and zeroes the carried
  * adjoint. */

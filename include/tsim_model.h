@@ -64,8 +64,15 @@ int tsim_model_update(tsim_model* m, int what, const char* name, const char* nam
  * -1 if there is no such record.
  *   TSIM_TAB_PAIR    key0 = general body or "ground", key1 = primitive body (ground pair: the body);  field 0 kn 1 kt 2 mu 3 damping, 4..7 shape 0..3
  *   TSIM_TAB_SENSOR  key0 = sensor name;                                                               field 0 kn 1 kt 2 mu 3 damping
- *   TSIM_TAB_DOF     key0 = joint name, field = dof of the joint (0 ..);                               the dof's damping */
-enum { TSIM_TAB_PAIR = 0, TSIM_TAB_SENSOR = 1, TSIM_TAB_DOF = 2 };
+ *   TSIM_TAB_DOF     key0 = joint name, field = dof of the joint (0 ..);                               the dof's damping
+ *   TSIM_TAB_LINK    key0 = joint name, key1 = part (decimal string) or NULL;                          field 0 mass, 1..3 centre of mass, 4..9 inertia (xx yy zz xy xz yz)
+ *                    The record of the link the joint's frame is attached to.  A free3d-* joint is compiled to several links: NULL names the
+ *                    last one, which carries the body's mass, "0", "1", ... the massless ones before it (and the last).  A fixed joint names the
+ *                    link its body was merged into; a joint fixed to the world has no record.
+ *   TSIM_TAB_MOTOR   key0 = joint name, field = 4 (dof of the joint) + {0 lo, 1 hi, 2 P, 3 D};           the (first) motor on that dof
+ *   TSIM_TAB_LIMIT   key0 = joint name, field = 3 (dof of the joint) + {0 lim_lo, 1 lim_hi, 2 lim_k}
+ * (TSIM_TAB_LINK / MOTOR / LIMIT: the columns of tsim_set_param_grad_groups' TSIM_PG_INERTIAL / MOTOR / LIMIT) */
+enum { TSIM_TAB_PAIR = 0, TSIM_TAB_SENSOR = 1, TSIM_TAB_DOF = 2, TSIM_TAB_LINK = 3, TSIM_TAB_MOTOR = 4, TSIM_TAB_LIMIT = 5 };
 int tsim_model_table_offset(const tsim_model* m, int kind, const char* key0, const char* key1, int field);
 
 #ifdef __cplusplus

@@ -462,6 +462,9 @@ struct tsim_batch {
   // tsim_set_param_grad: the caller's table gradient [B][nfrec] (null: off), the adjoint solutions z [cap][B][nr] the adjoint launch saves for the
   // parameter pass, and that pass's partial sums [pg_chunks][B][ts_pg_count] (both allocated when the gradient is first asked for)
   void* dLdp = nullptr; void* zbuf = nullptr; void* pgpart = nullptr; int pg_chunks = 0;
+  // tsim_set_param_grad_groups: which groups of columns a launch adds to (TSIM_PG_*), and the body pass's partial sums
+  // [pg_chunks][B][ts_pgb_count] (allocated when a body group is first asked for)
+  int pg_groups = TS_PG_CONTACT; void* pgbpart = nullptr;
   // tsim_kernel_timing: HIP events around every launch of the simulation kernels, on the stream they are launched on
   int kt_on = 0;
   std::vector<KtPair> kt;           // pairs recorded since the last tsim_kernel_times
@@ -777,7 +780,7 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
   const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z;
-  p.variant = kernel == TS_K_PARAM_GRAD || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
   p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
@@ -926,6 +929,28 @@ static int launch_param_grad(tsim_batch* b, int n, int seed_stride, int frames, 
   return 0;
 }
 
+// ... and the body groups' pass (tsim_set_param_grad_groups): k_param_grad_body over the same sub-steps and chunks, then its reduction
+template <class R>
+static int launch_param_grad_body(tsim_batch* b, int n, hipStream_t st) {
+  const int nl = b->I[TSIM_IH_NL];
+  PgBodyArgs<R> p;
+  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = n; p.t_end = b->t_cur;
+  p.tape = (const R*)b->tape; p.z = (const R*)b->zbuf;
+  p.nchunk = pg_chunks_for(b, n); p.chunk_len = (n + p.nchunk - 1) / p.nchunk;
+  p.nchunk = (n + p.chunk_len - 1) / p.chunk_len;          // (no empty chunk)
+  p.P = ts_pgb_count(nl, b->nu, b->nr); p.part = (R*)b->pgbpart; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k; p.groups = b->pg_groups;
+  if (!b->pgbpart || p.nchunk > b->pg_chunks) return fail("param_grad: the body groups' partial-sum buffer is missing or too small");
+  TsPlan plan = ts_plan(b, TS_K_PARAM_GRAD_BODY, false, 0);
+  plan.grid *= p.nchunk;
+  if (!TsLaunch<void, false, R>::run(plan, st, p)) return fail("no k_param_grad_body instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  PgBodyReduceArgs<R> r{(const R*)b->pgbpart, p.nchunk, b->B, p.P, (R*)b->dLdp, b->nfrec, nl, b->nu, b->nr,
+                        b->I[TSIM_IH_FOFF_LINK], b->I[TSIM_IH_FOFF_MOTOR], b->I[TSIM_IH_FOFF_DOF], b->pg_groups};
+  ts_param_reduce_body_launch(r, st);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 template <class R>
 static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, const int32_t* tac_slot, const void* df_dq, const void* df_dvar, const void* df_dtac, void* df_du, hipStream_t st) {
   BwdArgs<R> a = bwd_args<R>(b);
@@ -939,7 +964,8 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
     if (!ts_launch<false, R>(plan, st, a, (R*)b->zbuf)) return fail("no k_backward instantiation for the launch plan");
   }
   HIPCHK(hipGetLastError());
-  if (b->dLdp) return launch_param_grad<R>(b, n, seed_stride, frames, tac_slot, df_dtac, st);
+  if (b->dLdp && (b->pg_groups & TS_PG_CONTACT) && launch_param_grad<R>(b, n, seed_stride, frames, tac_slot, df_dtac, st)) return 1;
+  if (b->dLdp && (b->pg_groups & ~TS_PG_CONTACT)) return launch_param_grad_body<R>(b, n, st);
   return 0;
 }
 
@@ -1023,7 +1049,7 @@ void tsim_batch_destroy(tsim_batch* b) {
   for (auto& k : b->kt) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
   for (hipEvent_t e : b->kt_free) (void)hipEventDestroy(e);
   (void)hipFree(b->dFenv); (void)hipFree(b->dI); (void)hipFree(b->dF); (void)hipFree(b->tape); (void)hipFree(b->lamq); (void)hipFree(b->lamv); (void)hipFree(b->evals); (void)hipFree(b->helped); (void)hipFree(b->gnorm); (void)hipFree(b->order); (void)hipFree(b->order_ep); (void)hipFree(b->prev); (void)hipFree(b->poseR); (void)hipFree(b->poseD); (void)hipFree(b->fposeR); (void)hipFree(b->fposeD); (void)hipFree(b->dKmask); (void)hipFree(b->dFlag);
-  (void)hipFree(b->zbuf); (void)hipFree(b->pgpart);
+  (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); (void)hipFree(b->pgbpart);
   delete b;
 }
 
@@ -1173,7 +1199,27 @@ int tsim_set_env_tables(tsim_batch* b, const void* tables, void* stream) {
 }
 int tsim_table_size(const tsim_batch* b) { return b->nfrec; }
 
+// the body pass's partial sums, once a body group is on and the gradient is asked for (the default mask never gets here)
+static int pg_body_alloc(tsim_batch* b) {
+  if (b->pgbpart || !(b->pg_groups & ~TS_PG_CONTACT)) return 0;
+  TS_DEVICE(b);
+  const size_t pb = (size_t)pg_chunks_for(b, b->cap) * b->B * ts_pgb_count(b->I[TSIM_IH_NL], b->nu, b->nr) * b->esz;
+  if (hipMalloc(&b->pgbpart, std::max<size_t>(pb, 8)) != hipSuccess) { (void)hipGetLastError(); b->pgbpart = nullptr; return fail("set_param_grad_groups: hipMalloc failed"); }
+  return 0;
+}
+
+int tsim_set_param_grad_groups(tsim_batch* b, int mask) {
+  if (!b) return fail("set_param_grad_groups: null batch");
+  if (mask < 0 || (mask & ~(TS_PG_CONTACT | TS_PG_INERTIAL | TS_PG_MOTOR | TS_PG_LIMIT))) return fail("set_param_grad_groups: unknown group in mask " + std::to_string(mask));
+  const int before = b->pg_groups;
+  b->pg_groups = mask;
+  if (b->dLdp && pg_body_alloc(b)) { b->pg_groups = before; return 1; }
+  return 0;
+}
+int tsim_get_param_grad_groups(const tsim_batch* b) { return b ? b->pg_groups : -1; }
+
 int tsim_set_param_grad(tsim_batch* b, void* dL_dtables) {
+  if (dL_dtables && pg_body_alloc(b)) return 1;
   if (dL_dtables && (!b->zbuf || !b->pgpart)) {
     TS_DEVICE(b);
     const int chunks = pg_chunks_for(b, b->cap);

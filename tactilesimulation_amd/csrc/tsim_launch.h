@@ -1,8 +1,8 @@
 // tsim_launch.h — launch plans of the simulation kernels and the one launcher that runs them.
 //
-// A plan (TsPlan, made by tsim_hip.hip ts_plan and nowhere else) names one instantiation of k_forward, k_backward, k_backward_z, k_debug_eval
-// or k_param_grad and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
-// (tsim_hip.hip; k_param_grad: tsim_param_grad.hip), or a compiled-in model (tsim_static.h), whose translation units hold nothing but the
+// A plan (TsPlan, made by tsim_hip.hip ts_plan and nowhere else) names one instantiation of k_forward, k_backward, k_backward_z, k_debug_eval,
+// k_param_grad or k_param_grad_body and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
+// (tsim_hip.hip; the parameter passes: tsim_param_grad.hip, tsim_param_grad_body.hip), or a compiled-in model (tsim_static.h), whose translation units hold nothing but the
 // explicit instantiations of TsLaunch for their view: they are built with flags of their own (host/buildhash.py HIP_UNITS).
 #pragma once
 #include <type_traits>
@@ -10,7 +10,7 @@
 #include "tsim_param_grad.h"
 #include "tsim_static_pusher.h"
 
-enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD };
+enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD, TS_K_PARAM_GRAD_BODY };
 // the view of a launch: the generic kernels, a compiled-in model fully static, or its structure-static twin (parameters at run time)
 enum { TS_KM_GENERIC = 0, TS_KM_STATIC = 1, TS_KM_PARAM = 2 };
 using TsParamPusher = TsParam<TsStaticPusher>;
@@ -36,13 +36,14 @@ constexpr bool ts_instantiated(int kernel, int ms_nrm, bool fp32, bool policy, b
   if ((expj && (nrm != 16 || lpe != 64)) || (nrm != 8 && nrm != 16) || (lpe != 16 && lpe != 32 && lpe != 64)) return false;
   if (policy && (nrm != 8 || expj || (kernel != TS_K_FORWARD && kernel != TS_K_BACKWARD))) return false;
   if (ms_nrm == 0) return !default_opts;
-  if (kernel == TS_K_PARAM_GRAD || nrm != ms_nrm || expj) return false;
+  if (kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || nrm != ms_nrm || expj) return false;
   if (default_opts) return kernel == TS_K_FORWARD && fp32 && lpe == 16;
   if (policy || kernel == TS_K_DEBUG_EVAL) return fp32 && lpe == 16;
   return fp32 || lpe != 16;
 }
 
 template <class R, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_param_grad(PgArgs<R> a);      // tsim_param_grad.hip
+template <class R, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_param_grad_body(PgBodyArgs<R> a);      // tsim_param_grad_body.hip
 
 template <int N> using TsInt = std::integral_constant<int, N>;
 template <bool B> using TsBool = std::integral_constant<bool, B>;
@@ -66,6 +67,7 @@ template <class MS, bool POLICY, class R> struct TsLaunch {
   static bool run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave = nullptr);      // zsave: k_backward_z (TS_K_BACKWARD_Z)
   static bool run(const TsPlan& p, hipStream_t st, const DbgArgs<R>& a);
   static bool run(const TsPlan& p, hipStream_t st, const PgArgs<R>& a);
+  static bool run(const TsPlan& p, hipStream_t st, const PgBodyArgs<R>& a);
 };
 
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a) {
@@ -87,6 +89,9 @@ template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(cons
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const PgArgs<R>& a) {
   return shape<TS_K_PARAM_GRAD>(p, [&](auto, auto expj, auto lpe) { hipLaunchKernelGGL((k_param_grad<R, expj, lpe>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
 }
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const PgBodyArgs<R>& a) {
+  return shape<TS_K_PARAM_GRAD_BODY>(p, [&](auto, auto expj, auto lpe) { hipLaunchKernelGGL((k_param_grad_body<R, expj, lpe>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
+}
 
 // ... in the plan's view
 template <bool POLICY, class R, class A, class... Z> bool ts_launch(const TsPlan& p, hipStream_t st, const A& a, Z... z) {
@@ -94,7 +99,7 @@ template <bool POLICY, class R, class A, class... Z> bool ts_launch(const TsPlan
   if (p.variant == TS_KM_PARAM) return TsLaunch<TsParamPusher, POLICY, R>::run(p, st, a, z...);
   return TsLaunch<void, POLICY, R>::run(p, st, a, z...);
 }
-// instantiated in their own units: tsim_static_pusher.hip, tsim_param_pusher.hip, their _policy twins, tsim_param_grad.hip
+// instantiated in their own units: tsim_static_pusher.hip, tsim_param_pusher.hip, their _policy twins, tsim_param_grad.hip, tsim_param_grad_body.hip
 extern template struct TsLaunch<TsStaticPusher, false, float>;
 extern template struct TsLaunch<TsStaticPusher, false, double>;
 extern template struct TsLaunch<TsStaticPusher, true, float>;
@@ -105,3 +110,5 @@ extern template struct TsLaunch<TsParamPusher, true, float>;
 extern template struct TsLaunch<TsParamPusher, true, double>;
 extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const PgArgs<float>&);
 extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PgArgs<double>&);
+extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const PgBodyArgs<float>&);
+extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PgBodyArgs<double>&);

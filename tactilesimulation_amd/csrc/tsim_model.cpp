@@ -543,6 +543,7 @@ struct Compiled {
   std::vector<std::pair<std::string, std::string>> pair_keys;
   std::vector<SensorRec> sensors;
   std::map<std::string, std::pair<int, int>> dof_of_joint;
+  std::map<std::string, std::vector<int>> links_of_joint;      // TSIM_TAB_LINK: a moving joint's own links in order; a fixed joint: the link it was merged into
 };
 
 MassProps body_props(const Body& B) {      // in the body's JOINT frame
@@ -826,6 +827,11 @@ Compiled compile_spec(const Spec& S) {
     for (int i = 1; i <= nl; ++i) if (links[i].joint == j) d0 = std::min(d0, links[i].dof0);
     C.dof_of_joint[S.joints[j].name] = {d0, nd};
   }
+  for (int j = 0; j < nj; ++j) {
+    std::vector<int>& L = C.links_of_joint[S.joints[j].name];
+    if (joint_ndof(S.joints[j].type) > 0) { for (int i = 1; i <= nl; ++i) if (links[i].joint == j) L.push_back(i); }
+    else if (link_of_joint[j] > 0) L.push_back(link_of_joint[j]);
+  }
   C.sensors = std::move(sensors);
   return C;
 }
@@ -972,6 +978,23 @@ int tsim_model_table_offset(const tsim_model* m, int kind, const char* key0, con
   } else if (kind == TSIM_TAB_DOF) {
     auto it = m->c.dof_of_joint.find(key0);
     if (it != m->c.dof_of_joint.end() && field >= 0 && field < it->second.second) return I[TSIM_IH_FOFF_DOF] + (it->second.first + field) * TSIM_DF_SIZE + TSIM_DF_DAMPING;
+  } else if (kind == TSIM_TAB_LINK && field >= 0 && field < 10) {
+    auto it = m->c.links_of_joint.find(key0);
+    if (it != m->c.links_of_joint.end() && !it->second.empty()) {
+      const std::vector<int>& L = it->second;
+      long part = (long)L.size() - 1;
+      if (key1) { char* end = nullptr; part = std::strtol(key1, &end, 10); if (end == key1 || *end) part = -1; }
+      if (part >= 0 && part < (long)L.size()) return I[TSIM_IH_FOFF_LINK] + (L[part] - 1) * TSIM_LF_SIZE + TSIM_LF_MASS + field;      // mass, com, inertia: contiguous
+    }
+  } else if (kind == TSIM_TAB_MOTOR || kind == TSIM_TAB_LIMIT) {
+    const int per = kind == TSIM_TAB_MOTOR ? 4 : 3;
+    auto it = m->c.dof_of_joint.find(key0);
+    if (it != m->c.dof_of_joint.end() && field >= 0 && field < per * it->second.second) {
+      const int dof = it->second.first + field / per, f = field % per;
+      if (kind == TSIM_TAB_LIMIT) return I[TSIM_IH_FOFF_DOF] + dof * TSIM_DF_SIZE + TSIM_DF_LIM_LO + f;
+      for (int n = 0; n < I[TSIM_IH_NU]; ++n)
+        if (I[I[TSIM_IH_OFF_MOTOR] + n * TSIM_MI_SIZE + TSIM_MI_DOF] == dof) return I[TSIM_IH_FOFF_MOTOR] + n * TSIM_MF_SIZE + TSIM_MF_LO + f;
+    }
   }
   tsim_fail_("tsim_model_table_offset: no such record");
   return -1;

@@ -29,5 +29,30 @@ template <class R> struct PgReduceArgs {
   int npair, nsensor, nr, foff_pair, foff_sensor, foff_dof;
 };
 
+// The body groups (tsim_set_param_grad_groups: TSIM_PG_INERTIAL / MOTOR / LIMIT), a pass of their own (k_param_grad_body) with its own compact vector:
+// [link mass com(3) inertia(6)] x nl, [motor lo hi P D] x nu, [dof lim_lo lim_hi lim_k] x nr.  It evaluates the taped state WITH the sub-step's
+// discrete accelerations (the contact pass needs none) and reads the tape records before the sub-step for them.
+__host__ __device__ inline int ts_pgb_count(int nl, int nu, int nr) { return 10 * nl + 4 * nu + 3 * nr; }
+enum { TS_PG_CONTACT = 1, TS_PG_INERTIAL = 2, TS_PG_MOTOR = 4, TS_PG_LIMIT = 8 };      // = TSIM_PG_* of include/tsim.h
+
+template <class R> struct PgBodyArgs {
+  const int* I; const R* F; const R* Fenv; int fstride;
+  int B, n, t_end;
+  const R* tape; const R* z;                         // as PgArgs
+  int nchunk, chunk_len;
+  int P;                                             // ts_pgb_count
+  R* part;                                           // [nchunk][B][P] partial sums
+  int stage_cpt, tk;
+  int groups;                                        // TS_PG_*: the groups that are evaluated
+};
+template <class R> struct PgBodyReduceArgs {
+  const R* part; int nchunk, B, P;
+  R* out; int stride;
+  int nl, nu, nr, foff_link, foff_motor, foff_dof;
+  int groups;                                        // only these groups' columns are added to
+};
+
 void ts_param_reduce_launch(const PgReduceArgs<float>& a, hipStream_t st);
 void ts_param_reduce_launch(const PgReduceArgs<double>& a, hipStream_t st);
+void ts_param_reduce_body_launch(const PgBodyReduceArgs<float>& a, hipStream_t st);
+void ts_param_reduce_body_launch(const PgBodyReduceArgs<double>& a, hipStream_t st);

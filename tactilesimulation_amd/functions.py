@@ -194,7 +194,8 @@ class BatchedEpisodicParamSimFunction(autograd.Function):
     BatchedEpisodicSimFunction with the environments' numeric tables (BatchSim.set_env_tables: one row per environment, the model's F[] layout)
     as an input: forward sets them and runs the episode, backward returns next to the q0 / qdot0 / action gradients (the same numbers as
     BatchedEpisodicSimFunction's) the gradient w.r.t. the tables.  It is non-zero only at model.param_columns() — contact pair and tactile
-    sensor kn kt mu damping, dof damping; masses, geometry and the rest of a row are not differentiated.  A shared parameter is
+    sensor kn kt mu damping, dof damping — and, once batch_sim.set_param_grad_groups switched them on, at model.body_param_columns(): link
+    mass / centre of mass / inertia, motor lo hi P D, dof limits.  Geometry and the rest of a row are not differentiated.  A shared parameter is
     `base.expand(B, -1)`: autograd sums the rows.  The tables stay set on the batch after forward (its backward needs them)."""
 
     @staticmethod

@@ -97,7 +97,7 @@ class BatchSim:
     def set_param_grad(self, buf):
         """Table gradient (include/tsim.h tsim_set_param_grad): while `buf` ([B, table_size] of the batch's dtype, on its device) is set, every
         backward_steps / backward_episode ADDS dL/d(entry) to it for the columns model.param_columns() names (contact pair and sensor kn kt mu
-        damping, dof damping) and leaves the other columns untouched.  None switches it off.  The batch keeps a reference to the buffer."""
+        damping, dof damping; with set_param_grad_groups also those of model.body_param_columns()) and leaves the other columns untouched.  None switches it off.  The batch keeps a reference to the buffer."""
         if buf is not None:
             n = capi.lib().tsim_table_size(self._h)
             if buf.device != self.device or buf.dtype != self.dtype or tuple(buf.shape) != (self.B, n) or not buf.is_contiguous():
@@ -105,6 +105,21 @@ class BatchSim:
                                  % (self.B, n, self.dtype, self.device, tuple(buf.shape), buf.dtype, buf.device))
         capi.check(capi.lib().tsim_set_param_grad(self._h, _ptr(buf)))
         self._param_grad = buf
+
+    PARAM_GRAD_GROUPS = {"contact": 1, "inertial": 2, "motor": 4, "limit": 8}      # include/tsim.h TSIM_PG_*
+
+    def set_param_grad_groups(self, groups=("contact",)):
+        """Which groups of columns set_param_grad's buffer receives (include/tsim.h tsim_set_param_grad_groups): 'contact' (the default:
+        model.param_columns()), and the body groups 'inertial', 'motor', 'limit' (model.body_param_columns(): link mass / centre of mass /
+        inertia, motor lo hi P D, dof limits).  Takes effect with the next backward launch."""
+        mask = 0
+        for g in ([groups] if isinstance(groups, str) else groups):
+            mask |= self.PARAM_GRAD_GROUPS[g]
+        capi.check(capi.lib().tsim_set_param_grad_groups(self._h, mask))
+
+    def param_grad_groups(self):
+        mask = capi.lib().tsim_get_param_grad_groups(self._h)
+        return tuple(g for g, bit in self.PARAM_GRAD_GROUPS.items() if mask & bit)
 
     def reset(self, q0, qd0=None, backward_flag=False):
         q0 = self._chk(q0, self.ndof_r, "q0")

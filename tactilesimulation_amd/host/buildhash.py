@@ -65,6 +65,7 @@ HIP_UNITS = [("tsim_hip.hip", []), ("tsim_static_pusher.hip", ["-ffinite-math-on
              ("tsim_static_pusher_policy.hip", ["-ffinite-math-only", "-fno-signed-zeros"]),      # (closed-loop instantiations: 76 KB at -O2, stay at -Os)
              ("tsim_param_pusher_policy.hip", ["-ffinite-math-only", "-fno-signed-zeros"]),       # ... of the structure-static kernels (round 6: closed loop with per-environment tables)
              ("tsim_param_grad.hip", []),                                                         # the parameter-gradient pass (tsim_set_param_grad): generic flags
+             ("tsim_param_grad_body.hip", []),                                                    # its body groups (tsim_set_param_grad_groups): a unit of their own, so that k_param_grad's code does not move
              ("tsim_model.cpp", ["-ffp-contract=off"])]                                           # host only: the model loader (include/tsim_model.h); plain double arithmetic, no contraction
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC"]      # units that are not .hip: no device code
 

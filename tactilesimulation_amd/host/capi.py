@@ -22,6 +22,7 @@ _SIGS = {
     "tsim_reset": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "tsim_set_env_tables": (C.c_int, [_vp, _vp, _vp]), "tsim_table_size": (C.c_int, [_vp]),
     "tsim_set_param_grad": (C.c_int, [_vp, _vp]),
+    "tsim_set_param_grad_groups": (C.c_int, [_vp, C.c_int]), "tsim_get_param_grad_groups": (C.c_int, [_vp]),
     "tsim_reset_masked": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "tsim_step": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tsim_get_state": (C.c_int, [_vp, _vp, _vp, _vp]),

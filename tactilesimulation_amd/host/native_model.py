@@ -10,7 +10,10 @@ from . import capi
 
 UPD = {"joint_damping": 0, "joint_location": 1, "body_density": 2, "body_size": 3, "endeffector_position": 4, "contact_parameters": 5,
        "tactile_parameters": 6, "virtual_object": 7}
-TAB = {"pair": 0, "sensor": 1, "dof": 2}
+TAB = {"pair": 0, "sensor": 1, "dof": 2, "link": 3, "motor": 4, "limit": 5}
+LINK_FIELDS = ("mass", "com_x", "com_y", "com_z", "ixx", "iyy", "izz", "ixy", "ixz", "iyz")
+MOTOR_FIELDS = ("lo", "hi", "P", "D")
+LIMIT_FIELDS = ("lo", "hi", "k")
 PAIR_FIELDS = {"kn": 0, "kt": 1, "mu": 2, "damping": 3, "shape0": 4, "shape1": 5, "shape2": 6, "shape3": 7}
 
 
@@ -50,6 +53,18 @@ class NativeModel:
                                              v.ctypes.data_as(C.POINTER(C.c_double)), len(v)))
 
     def table_offset(self, kind, key0, key1=None, field=0):
+        """tsim_model_table_offset.  'link', 'motor' and 'limit' also take CompiledModel.table_offset's keys: key0 = (joint, part) / (joint, k)
+        and a field name."""
+        if kind == "link":
+            if isinstance(key0, tuple):
+                key0, key1 = key0[0], None if key0[1] is None else str(key0[1])
+            field = LINK_FIELDS.index(field) if isinstance(field, str) else field
+        elif kind in ("motor", "limit"):
+            names = MOTOR_FIELDS if kind == "motor" else LIMIT_FIELDS
+            k = 0
+            if isinstance(key0, tuple):
+                key0, k = key0
+            field = len(names) * k + names.index(field) if isinstance(field, str) else field
         if kind == "pair":
             field = PAIR_FIELDS[field] if isinstance(field, str) else field
         elif kind == "sensor":

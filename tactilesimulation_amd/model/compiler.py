@@ -258,7 +258,12 @@ class CompiledModel:
     def table_offset(self, kind, key, field):
         """Index into F[] of one numeric parameter, for per-environment tables (BatchSim.set_env_tables).
         kind 'pair': key = (general_body | 'ground', primitive_body | body), field in kn kt mu damping shape0..3;
-        kind 'sensor': key = sensor name, field in kn kt mu damping; kind 'dof': key = (joint name, k), field damping."""
+        kind 'sensor': key = sensor name, field in kn kt mu damping; kind 'dof': key = (joint name, k), field damping;
+        kind 'link': key = (joint name, part), field in LINK_FIELDS — the record of the link the joint's frame is attached to; a free3d-* joint
+        is compiled to several links: part None is the last one, which carries the body's mass, 0, 1, ... the massless ones before it; a fixed
+        joint names the link its body was merged into (fixed to the world: KeyError);
+        kind 'motor': key = (joint name, k), field in lo hi P D — the (first) motor on dof k of the joint;
+        kind 'limit': key = (joint name, k), field in lo hi k."""
         I = self.I
         if kind == "pair":
             idx = [tuple(k) for k in self.meta["pair_keys"]].index(tuple(key))
@@ -272,9 +277,28 @@ class CompiledModel:
         if kind == "dof":
             d0, nd = self.meta["dof_of_joint"][key[0]]
             return int(I[B.TSIM_IH_FOFF_DOF]) + (d0 + key[1]) * B.TSIM_DF_SIZE + {"damping": B.TSIM_DF_DAMPING}[field]
+        if kind == "link":
+            name, part = (key, None) if isinstance(key, str) else key
+            links = self.meta["links_of_joint"][name]
+            if not links or (part is not None and not 0 <= part < len(links)):
+                raise KeyError(key)
+            return int(I[B.TSIM_IH_FOFF_LINK]) + (links[-1 if part is None else part] - 1) * B.TSIM_LF_SIZE + B.TSIM_LF_MASS + self.LINK_FIELDS.index(field)
+        if kind in ("motor", "limit"):
+            d0, nd = self.meta["dof_of_joint"][key[0]]
+            if not 0 <= key[1] < nd:
+                raise KeyError(key)
+            if kind == "limit":
+                return int(I[B.TSIM_IH_FOFF_DOF]) + (d0 + key[1]) * B.TSIM_DF_SIZE + B.TSIM_DF_LIM_LO + self.LIMIT_FIELDS.index(field)
+            for n in range(int(I[B.TSIM_IH_NU])):
+                if int(I[int(I[B.TSIM_IH_OFF_MOTOR]) + n * B.TSIM_MI_SIZE + B.TSIM_MI_DOF]) == d0 + key[1]:
+                    return int(I[B.TSIM_IH_FOFF_MOTOR]) + n * B.TSIM_MF_SIZE + B.TSIM_MF_LO + self.MOTOR_FIELDS.index(field)
+            raise KeyError(key)
         raise KeyError(kind)
 
     PARAM_FIELDS = ("kn", "kt", "mu", "damping")
+    LINK_FIELDS = ("mass", "com_x", "com_y", "com_z", "ixx", "iyy", "izz", "ixy", "ixz", "iyz")      # TSIM_LF_MASS .. TSIM_LF_INERTIA + 5
+    MOTOR_FIELDS = ("lo", "hi", "P", "D")
+    LIMIT_FIELDS = ("lo", "hi", "k")
 
     def param_columns(self):
         """[(kind, key, field, column)] of every table entry tsim_set_param_grad / BatchSim.set_param_grad computes a gradient for: per contact
@@ -287,6 +311,26 @@ class CompiledModel:
             cols += [("sensor", s, f, self.table_offset("sensor", s, f)) for f in self.PARAM_FIELDS]
         for j, (d0, nd) in sorted(self.meta["dof_of_joint"].items(), key=lambda kv: kv[1][0]):
             cols += [("dof", (j, k), "damping", self.table_offset("dof", (j, k), "damping")) for k in range(nd)]
+        return cols
+
+    def body_param_columns(self):
+        """[(kind, key, field, column)] of the entries the body groups of tsim_set_param_grad_groups / BatchSim.set_param_grad_groups add a
+        gradient for: per link record ('link', each once, under the joint that moves it) mass, centre of mass and inertia; per motor
+        ('motor') lo hi P D; per dof ('limit') lo hi k.  Disjoint from param_columns()."""
+        cols = []
+        for J in self.spec["joints"]:
+            if J["name"] in self.meta["dof_of_joint"]:
+                for part in range(len(self.meta["links_of_joint"][J["name"]])):
+                    cols += [("link", (J["name"], part), f, self.table_offset("link", (J["name"], part), f)) for f in self.LINK_FIELDS]
+        seen = set()
+        by_dof = {d0 + k: (j, k) for j, (d0, nd) in self.meta["dof_of_joint"].items() for k in range(nd)}
+        for n in range(int(self.I[B.TSIM_IH_NU])):      # (several motors on one dof: table_offset names the first, the others have no key)
+            d = int(self.I[int(self.I[B.TSIM_IH_OFF_MOTOR]) + n * B.TSIM_MI_SIZE + B.TSIM_MI_DOF])
+            if d not in seen:
+                seen.add(d)
+                cols += [("motor", by_dof[d], f, self.table_offset("motor", by_dof[d], f)) for f in self.MOTOR_FIELDS]
+        for j, (d0, nd) in sorted(self.meta["dof_of_joint"].items(), key=lambda kv: kv[1][0]):
+            cols += [("limit", (j, k), f, self.table_offset("limit", (j, k), f)) for k in range(nd) for f in self.LIMIT_FIELDS]
         return cols
 
     ndof_r = property(lambda s: int(s.I[B.TSIM_IH_NR]))
@@ -625,6 +669,8 @@ def compile_spec(spec):
         "link_of_joint": link_of_joint,
         "dof_of_joint": {J["name"]: (min(L["dof0"] for L in links[1:] if L["joint"] == j), B.JOINT_NDOF[J["type"]])
                          for j, J in enumerate(joints) if B.JOINT_NDOF[J["type"]] > 0},
+        "links_of_joint": {J["name"]: ([i for i in range(1, nl + 1) if links[i]["joint"] == j] if B.JOINT_NDOF[J["type"]] > 0
+                                       else [link_of_joint[j]] if link_of_joint[j] > 0 else []) for j, J in enumerate(joints)},
         "pair_keys": [p["key"] for p in pairs],
         "sensor_names": [s["name"] for s in sensors],
         "sensor_taxels": [(s["tax0"], s["ntax"], s["rows"], s["cols"]) for s in sensors],

@@ -76,6 +76,8 @@ def lib(native=False):
         L.orc_taxel_list.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.POINTER(C.c_int), _dp]
         L.orc_taxel_list.restype = C.c_int
         L.orc_set_param_grad.argtypes = [C.c_void_p, _dp]
+        L.orc_set_param_grad_groups.argtypes = [C.c_void_p, C.c_int]
+        L.orc_set_param_grad_groups.restype = C.c_int
         L.orc_table_size.argtypes = [C.c_void_p]
         L.orc_table_size.restype = C.c_int
         L.orc_inverse_dynamics.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
@@ -172,7 +174,7 @@ class OracleSim:
     def set_param_grad(self, buf):
         """Table gradient, the column convention of BatchSim.set_param_grad for one environment: while `buf` (float64 [table_size], C-contiguous,
         table_size = the model's per-environment table width, its float records before the contact points) is set, every backward_steps ADDS
-        dL/d(entry) to it for the columns model.param_columns() names and leaves the other columns untouched.  None switches it off.  The
+        dL/d(entry) to it for the columns model.param_columns() names (with set_param_grad_groups also model.body_param_columns()) and leaves the other columns untouched.  None switches it off.  The
         oracle keeps a reference to the buffer."""
         if buf is not None:
             if not (isinstance(buf, np.ndarray) and buf.dtype == np.float64 and buf.ndim == 1 and buf.flags.c_contiguous):
@@ -181,6 +183,18 @@ class OracleSim:
                 raise ValueError("set_param_grad: %d columns, the tables have %d" % (buf.size, self._L.orc_table_size(self._h)))
         self._pg = buf
         self._L.orc_set_param_grad(self._h, _p(buf))
+
+    PARAM_GRAD_GROUPS = {"contact": 1, "inertial": 2, "motor": 4, "limit": 8}      # include/tsim.h TSIM_PG_*
+
+    def set_param_grad_groups(self, names):
+        """Which groups of columns set_param_grad's buffer receives, as BatchSim.set_param_grad_groups: "contact" (model.param_columns(), the
+        default) and the body groups "inertial", "motor", "limit" (model.body_param_columns()).  The contact columns, dL/du and the carried
+        adjoint do not change with the body groups on."""
+        mask = 0
+        for n in names:
+            mask |= self.PARAM_GRAD_GROUPS[n]
+        if self._L.orc_set_param_grad_groups(self._h, mask) != 0:
+            raise ValueError("set_param_grad_groups: bad mask %d" % mask)
 
     def adjoint(self):
         a, b = np.zeros(self.nr), np.zeros(self.nr)

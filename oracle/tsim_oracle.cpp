@@ -199,12 +199,17 @@ template <class T> static inline void prim_pose(const Model& m, int pk, const Li
 }
 
 // Parameter override (parameter adjoint only): Dual seeds for the contact pairs' (kn, kt, mu, kd) [4 npair], the sensors' [4 nsensor] and the
-// dofs' damping [nr]; a null table reads the blob's values as before.
-struct ParamSrc { const Dual* pair = nullptr; const Dual* sensor = nullptr; const Dual* damp = nullptr; };
+// dofs' damping [nr]; for the body groups the links' (mass, com xyz, inertia xx yy zz xy xz yz) [10 nl], the motors' (lo, hi, P, D) [4 nu] and the
+// dofs' (lim_lo, lim_hi, lim_k) [3 nr], each in blob order.  A null table reads the blob's values as before.
+struct ParamSrc { const Dual* pair = nullptr; const Dual* sensor = nullptr; const Dual* damp = nullptr;
+                  const Dual* link = nullptr; const Dual* motor = nullptr; const Dual* limit = nullptr; };
+// the override applies to the Dual instantiations only (a double evaluation never has one)
+template <class T> static inline T damp_p(const Dual&) { abort(); }
+template <> inline Dual damp_p<Dual>(const Dual& d) { return d; }
 
 // ------------------------------------------------------------------------------------------ kinematics + RNEA residual
 template <class T>
-static void kinematics(const Model& m, const T* q, const T* qd, const T* qdd, Link<T>* L, V3<T>* Ww, V3<T>* Wv, bool dyn) {
+static void kinematics(const Model& m, const T* q, const T* qd, const T* qdd, Link<T>* L, V3<T>* Ww, V3<T>* Wv, bool dyn, const ParamSrc* ps = nullptr) {
   Link<T>& W0 = L[0];
   for (int i = 0; i < 9; ++i) W0.R.m[i] = T(i % 4 == 0 ? 1.0 : 0.0);
   W0.p = mk<T>(T(0.0), T(0.0), T(0.0)); W0.w = W0.p; W0.v = W0.p; W0.aw = W0.p;
@@ -264,10 +269,12 @@ static void kinematics(const Model& m, const T* q, const T* qd, const T* qdd, Li
     if (has_b) { X.aw = X.aw + extra_b; X.av = X.av + cross(X.p, extra_b); }
     if (!dyn) continue;
     // inertial wrench about the world origin
-    T mass = T(lf[TSIM_LF_MASS]);
-    V3<T> c = mul(X.R, cvec<T>(lf + TSIM_LF_COM)) + X.p;
-    const double* ii = lf + TSIM_LF_INERTIA;
-    M3<T> Il; Il.m[0] = T(ii[0]); Il.m[4] = T(ii[1]); Il.m[8] = T(ii[2]); Il.m[1] = Il.m[3] = T(ii[3]); Il.m[2] = Il.m[6] = T(ii[4]); Il.m[5] = Il.m[7] = T(ii[5]);
+    T lp[10];                                                // mass, com xyz, inertia xx yy zz xy xz yz (contiguous in the blob)
+    for (int e = 0; e < 10; ++e) lp[e] = ps && ps->link ? damp_p<T>(ps->link[10 * (i - 1) + e]) : T(lf[TSIM_LF_MASS + e]);
+    T mass = lp[0];
+    V3<T> c = mul(X.R, mk<T>(lp[1], lp[2], lp[3])) + X.p;
+    const T* ii = lp + 4;
+    M3<T> Il; Il.m[0] = ii[0]; Il.m[4] = ii[1]; Il.m[8] = ii[2]; Il.m[1] = Il.m[3] = ii[3]; Il.m[2] = Il.m[6] = ii[4]; Il.m[5] = Il.m[7] = ii[5];
     V3<T> vc = X.v + cross(X.w, c);
     V3<T> ac = X.av + cross(X.aw, c) + cross(X.w, vc);
     V3<T> f = ac * mass;
@@ -277,17 +284,14 @@ static void kinematics(const Model& m, const T* q, const T* qd, const T* qdd, Li
   }
 }
 
-// the override applies to the Dual instantiations only (a double evaluation never has one)
 template <class T> static inline bool contact_force_p(int, const double*, const Dual*, const M3<T>&, const V3<T>&, const V3<T>&, const V3<T>&, V3<T>&) { abort(); }
 template <> inline bool contact_force_p<Dual>(int prim, const double* shape, const Dual* k, const M3<Dual>& RP, const V3<Dual>& pP, const V3<Dual>& xw,
                                              const V3<Dual>& vrel, V3<Dual>& Fw) { return contact_force<Dual, Dual>(prim, shape, k, RP, pP, xw, vrel, Fw); }
-template <class T> static inline T damp_p(const Dual&) { abort(); }
-template <> inline Dual damp_p<Dual>(const Dual& d) { return d; }
 
 template <class T>
 static void residual(const Model& m, const T* q, const T* qd, const T* qdd, const T* u, T* r, Link<T>* L, const ParamSrc* ps = nullptr) {
   V3<T> Ww[MAXR], Wv[MAXR];
-  kinematics(m, q, qd, qdd, L, Ww, Wv, true);
+  kinematics(m, q, qd, qdd, L, Ww, Wv, true, ps);
   // contacts (dynamics-active pairs)
   for (int pk = 0; pk < m.npair; ++pk) {
     const int* pi = m.pi(pk); const double* pf = m.pf(pk);
@@ -322,20 +326,24 @@ static void residual(const Model& m, const T* q, const T* qd, const T* qdd, cons
   for (int k = 0; k < m.nr; ++k) {
     const double* df = m.df(k);
     r[k] = r[k] + qd[k] * (ps && ps->damp ? damp_p<T>(ps->damp[k]) : T(df[TSIM_DF_DAMPING]));
-    if (df[TSIM_DF_LIM_K] > 0) {
-      if (val(q[k]) < df[TSIM_DF_LIM_LO]) r[k] = r[k] - (T(df[TSIM_DF_LIM_LO]) - q[k]) * T(df[TSIM_DF_LIM_K]);
-      else if (val(q[k]) > df[TSIM_DF_LIM_HI]) r[k] = r[k] + (q[k] - T(df[TSIM_DF_LIM_HI])) * T(df[TSIM_DF_LIM_K]);
+    if (df[TSIM_DF_LIM_K] > 0) {                             // (the branches read the blob's values: an override only carries tangents)
+      const bool ov = ps && ps->limit;
+      if (val(q[k]) < df[TSIM_DF_LIM_LO]) r[k] = r[k] - ((ov ? damp_p<T>(ps->limit[3 * k]) : T(df[TSIM_DF_LIM_LO])) - q[k]) * (ov ? damp_p<T>(ps->limit[3 * k + 2]) : T(df[TSIM_DF_LIM_K]));
+      else if (val(q[k]) > df[TSIM_DF_LIM_HI]) r[k] = r[k] + (q[k] - (ov ? damp_p<T>(ps->limit[3 * k + 1]) : T(df[TSIM_DF_LIM_HI]))) * (ov ? damp_p<T>(ps->limit[3 * k + 2]) : T(df[TSIM_DF_LIM_K]));
     }
   }
   for (int j = 0; j < m.nu; ++j) {
     const int* mi = m.mi(j); const double* mf = m.mf(j);
     int k = mi[TSIM_MI_DOF];
+    const bool ov = ps && ps->motor;
     if (mi[TSIM_MI_CTRL] == 0) {
       T uc = u[j];
       if (val(uc) > 1.0) uc = T(1.0); else if (val(uc) < -1.0) uc = T(-1.0);
-      r[k] = r[k] - (T(mf[TSIM_MF_LO]) + (uc + T(1.0)) * T(0.5 * (mf[TSIM_MF_HI] - mf[TSIM_MF_LO])));
+      if (ov) { T lo = damp_p<T>(ps->motor[4 * j]), hi = damp_p<T>(ps->motor[4 * j + 1]); r[k] = r[k] - (lo + (uc + T(1.0)) * ((hi - lo) * T(0.5))); }
+      else r[k] = r[k] - (T(mf[TSIM_MF_LO]) + (uc + T(1.0)) * T(0.5 * (mf[TSIM_MF_HI] - mf[TSIM_MF_LO])));
     } else {
-      r[k] = r[k] - ((u[j] - q[k]) * T(mf[TSIM_MF_P]) - qd[k] * T(mf[TSIM_MF_D]));
+      if (ov) r[k] = r[k] - ((u[j] - q[k]) * damp_p<T>(ps->motor[4 * j + 2]) - qd[k] * damp_p<T>(ps->motor[4 * j + 3]));
+      else r[k] = r[k] - ((u[j] - q[k]) * T(mf[TSIM_MF_P]) - qd[k] * T(mf[TSIM_MF_D]));
     }
   }
 }
@@ -467,6 +475,7 @@ struct Sim {
   long newton_iters = 0, substeps = 0, nonconv = 0, evals = 0;
   long kicks = 0, restarts = 0, trust = 0, ls_exhausted = 0;   // how often each globalisation device acted (kernel mode) / a line search ran out (literal mode)
   double* dLdF = nullptr;  // orc_set_param_grad: table gradient the adjoint adds to (the blob's float records, columns < FOFF_CPT)
+  int pg_groups = 1;       // orc_set_param_grad_groups: which groups of columns (the bits of include/tsim.h TSIM_PG_*; default: contact only)
 };
 
 // One implicit step in predictor form (covers BDF1 and BDF2):
@@ -703,6 +712,39 @@ static void param_vjp_dyn(const Model& m, const double* q1, const StepCoef& c, c
     g_nd = 0;
   }
 }
+// The body groups (orc_set_param_grad_groups; include/tsim.h TSIM_PG_INERTIAL = 2, MOTOR = 4, LIMIT = 8): the same -z^T dg/dp at the same taped
+// point for the links' mass, centre of mass and inertia, the motors' lo hi P D and the dofs' lim_lo lim_hi lim_k.  A pass of its own: what
+// param_vjp_dyn adds does not change with it.  The limit columns of a dof without a limit (lim_k == 0) never enter r: exactly 0.
+static void param_vjp_body(const Model& m, int groups, const double* q1, const StepCoef& c, const double* u, const double* z, double* dLdF) {
+  const int nr = m.nr, nlk = 10 * m.nl, nmo = 4 * m.nu, nli = 3 * nr;
+  std::vector<int> seed;                                            // index into (link | motor | limit) seed tables laid end to end
+  if (groups & 2) for (int i = 0; i < nlk; ++i) seed.push_back(i);
+  if (groups & 4) for (int i = 0; i < nmo; ++i) seed.push_back(nlk + i);
+  if (groups & 8) for (int i = 0; i < nli; ++i) seed.push_back(nlk + nmo + i);
+  std::vector<Dual> tab(std::max(nlk + nmo + nli, 1));
+  for (int c0 = 0; c0 < (int)seed.size(); c0 += NDMAX) {
+    const int nd = std::min(NDMAX, (int)seed.size() - c0);
+    g_nd = nd;
+    Dual q[MAXR], qd[MAXR], qa[MAXR], uu[MAXR], r[MAXR]; Link<Dual> L[MAXL];
+    for (int k = 0; k < nr; ++k) { double d = q1[k] - c.qpred[k]; q[k] = Dual(q1[k]); qd[k] = Dual(c.qdpred[k] + c.cv * d); qa[k] = Dual(c.ca * d); }
+    for (int j = 0; j < m.nu; ++j) uu[j] = Dual(u[j]);
+    for (int i = 0; i < nlk; ++i) tab[i] = Dual(m.lf(i / 10 + 1)[TSIM_LF_MASS + i % 10]);
+    for (int i = 0; i < nmo; ++i) tab[nlk + i] = Dual(m.mf(i >> 2)[TSIM_MF_LO + (i & 3)]);
+    for (int i = 0; i < nli; ++i) tab[nlk + nmo + i] = Dual(m.df(i / 3)[TSIM_DF_LIM_LO + i % 3]);
+    for (int d = 0; d < nd; ++d) tab[seed[c0 + d]].d[d] = 1.0;
+    ParamSrc ps; ps.link = tab.data(); ps.motor = tab.data() + nlk; ps.limit = tab.data() + nlk + nmo;
+    residual<Dual>(m, q, qd, qa, uu, r, L, &ps);
+    for (int d = 0; d < nd; ++d) {
+      double s = 0; for (int i = 0; i < nr; ++i) s += z[i] * r[i].d[d];
+      const int sd = seed[c0 + d];
+      const int col = sd < nlk ? m.I[TSIM_IH_FOFF_LINK] + (sd / 10) * TSIM_LF_SIZE + TSIM_LF_MASS + sd % 10
+                    : sd < nlk + nmo ? m.I[TSIM_IH_FOFF_MOTOR] + ((sd - nlk) >> 2) * TSIM_MF_SIZE + TSIM_MF_LO + ((sd - nlk) & 3)
+                                     : m.I[TSIM_IH_FOFF_DOF] + ((sd - nlk - nmo) / 3) * TSIM_DF_SIZE + TSIM_DF_LIM_LO + (sd - nlk - nmo) % 3;
+      dLdF[col] -= s / c.ca;
+    }
+    g_nd = 0;
+  }
+}
 // ... and of a seeded output frame at state (q, qd): dL/dp += wtac^T dtac/dp for the sensors' (kn, kt, mu, kd)
 static void param_vjp_tac(const Model& m, const double* q0, const double* qd0, const double* wtac, double* dLdF) {
   const int nr = m.nr, ntac3 = 3 * m.ntax, np = 4 * m.nsensor;
@@ -810,7 +852,8 @@ int orc_backward_steps(void* h, int n, const double* df_dq, const double* df_dva
     if (nu > 0) eval_g_jac_c(m, r.q1.data(), c, r.u.data(), 3, g.data(), Ju.data());
     for (int k = 0; k < nr; ++k) rhs[k] = S.lam_q[k] + c.cv * S.lam_v[k];               // d qd1 / d q1 = cv
     if (!solve_dense(nr, H.data(), rhs.data(), z.data(), true)) return -2;
-    if (S.dLdF) {
+    if (S.dLdF && (S.pg_groups & ~1)) param_vjp_body(m, S.pg_groups, r.q1.data(), c, r.u.data(), z.data(), S.dLdF);
+    if (S.dLdF && (S.pg_groups & 1)) {
       param_vjp_dyn(m, r.q1.data(), c, r.u.data(), z.data(), S.dLdF);
       if (df_dtac) param_vjp_tac(m, r.q1.data(), r.qd1.data(), df_dtac + (size_t)j * 3 * m.ntax, S.dLdF);
     }
@@ -842,6 +885,9 @@ int orc_backward_steps(void* h, int n, const double* df_dq, const double* df_dva
 // per-environment tables hold, < FOFF_CPT, are touched) is set, orc_backward_steps ADDS dL/d(entry) to it for every contact pair's and tactile
 // sensor's kn kt mu kd and every dof's damping.  nullptr switches it off.
 void orc_set_param_grad(void* h, double* dL_dF) { ((Sim*)h)->dLdF = dL_dF; }
+// Which groups orc_backward_steps adds to dL_dF: a mask of include/tsim.h's TSIM_PG_* (1 contact — the columns above, the default; 2 inertial:
+// per link mass, com, inertia; 4 motor: lo hi P D; 8 limit: lim_lo lim_hi lim_k).  Returns -1 for unknown bits.
+int orc_set_param_grad_groups(void* h, int mask) { if (mask < 0 || (mask & ~15)) return -1; ((Sim*)h)->pg_groups = mask; return 0; }
 int orc_table_size(void* h) { return ((Sim*)h)->m.I[TSIM_IH_FOFF_CPT]; }
 void orc_get_adjoint(void* h, double* lam_q, double* lam_v) { Sim& S = *(Sim*)h; for (int k = 0; k < S.m.nr; ++k) { lam_q[k] = S.lam_q[k]; lam_v[k] = S.lam_v[k]; } }
 void orc_clear_adjoint(void* h) { Sim& S = *(Sim*)h; std::fill(S.lam_q.begin(), S.lam_q.end(), 0.0); std::fill(S.lam_v.begin(), S.lam_v.end(), 0.0); std::fill(S.lam_q1.begin(), S.lam_q1.end(), 0.0); std::fill(S.lam_v1.begin(), S.lam_v1.end(), 0.0); }

@@ -1,0 +1,144 @@
+"""The CPU-only yardstick of the body groups of the table gradient (link inertia, motors, limits), shared by tests/test_gpu_body_param_grad.py (the
+kernels against the oracle's finite differences), tests/test_oracle_body_param_grad.py (the oracle's exact body adjoint against the same
+differences) and tests/test_gpu_body_param_grad_oracle.py (the kernels against that adjoint).  No GPU, no torch: the functions here run in spawned
+processes side by side."""
+import copy
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import tactilesimulation_amd.model.blob as Bl      # noqa: E402
+from tactilesimulation_amd.model.compiler import load_model      # noqa: E402
+from test_oracle_param_grad import case, loss_weights, oracle_episode      # noqa: E402
+
+BODY = ("inertial", "motor", "limit")
+ALL = ("contact",) + BODY
+KINDS = ("mass", "com", "inertia", "motor lo", "motor hi", "motor P", "motor D", "limit lo", "limit hi", "limit k")
+# (name, frames)
+MODELS = [("pusher", 4), ("tactile_insertion", 3), ("stable_grasp", 3), ("dclaw_position_control", 3), ("tactile_pad", 3), ("box_slide", 4),
+          ("pad_press", 4), ("slider_push", 4), ("ball_push", 4), ("bdf2:ball_push", 3), ("bdf2:tactile_pad", 3), ("small:3", 4), ("small:11", 4),
+          ("large:L3", 4), ("large:L7", 4), ("large:L16", 4), ("limit_push", 4)]
+# a second model whose lower AND upper limit springs act in every environment, without contact (so that fp32 keeps the oracle's branches): the
+# files that hold something to the oracle's exact adjoint run it beside MODELS
+LIMIT_CHAIN = ("limit_chain", 4)
+
+
+def kind_of(bc):
+    kind, _, f, _ = bc
+    return {"link": "mass" if f == "mass" else "com" if f.startswith("com") else "inertia"}.get(kind) or "%s %s" % (kind, f)
+
+
+def body_case(name, B, T):
+    """case() of tests/test_oracle_param_grad.py, and this file's own model: tests/models/limit_push.xml — a slider a force motor pushes below its
+    lower limit and an arm a position motor holds above its upper limit, both in the limit from the first sub-step on"""
+    if name == "limit_chain":      # tests/models/limit_chain.xml: the shoulder below its lower limit, the elbow above its upper one
+        m = load_model(os.path.join(HERE, "models", "limit_chain.xml"))
+        q0 = np.tile([[-0.25, 0.3]], (B, 1))
+        u = np.tile(np.array([[-0.6, 0.5], [-0.4, 0.45], [-0.7, 0.55], [-0.5, 0.4]])[None], (B, 1, 1))[:, :T]
+        return m, q0, np.zeros_like(q0), u, 2
+    if name != "limit_push":
+        return case(name, B, T)
+    m = load_model(os.path.join(HERE, "models", "limit_push.xml"))
+    q0 = np.tile([[-0.03, 0.25]], (B, 1))
+    u = np.tile(np.array([[-0.8, 0.6], [-0.6, 0.7], [-0.9, 0.5], [-0.7, 0.6]])[None], (B, 1, 1))[:, :T]
+    return m, q0, np.zeros_like(q0), u, 2
+
+
+def _step(m, bc):
+    """h of the yardstick for one column"""
+    kind, _, f, c = bc
+    if kind != "link":
+        return 1e-4 * max(abs(float(m.F[c])), 1.0)
+    base = c - (c - int(m.I[Bl.TSIM_IH_FOFF_LINK])) % Bl.TSIM_LF_SIZE
+    mass = abs(float(m.F[base + Bl.TSIM_LF_MASS]))
+    imax = float(np.abs(m.F[base + Bl.TSIM_LF_INERTIA:base + Bl.TSIM_LF_INERTIA + 6]).max())
+    return 1e-3 * {"mass": max(mass, 1e-3), "com": 1e-2, "inertia": max(imax, 1e-6)}[kind_of(bc)]
+
+
+def _differences(name, T, tol=1e-13, only=None):
+    """the oracle runs of one model (CPU only) at Newton tolerance `tol`: R1, R2, kept, exact0 per new column (only: the indices of the columns to
+    difference, the others stay not kept), the base run's signatures and loss"""
+    m, q0, qd0, u, S = body_case(name, 1, T)
+    m = copy.deepcopy(m)
+    m.F[Bl.TSIM_FH_TOL] = tol
+    cols = m.body_param_columns()
+    w = loss_weights(m, u.shape[1], 1)
+    L0, _, sig0, bad0, _ = oracle_episode(m, q0[0], u[0], S, w, grad=False, qd0=qd0[0])
+    assert bad0 == 0, name
+    R1, R2 = np.full(len(cols), np.nan), np.full(len(cols), np.nan)
+    kept, exact0 = np.zeros(len(cols), bool), np.zeros(len(cols), bool)
+    for i, bc in enumerate(cols):
+        if only is not None and i not in only:
+            continue
+        c, p, h = bc[3], float(m.F[bc[3]]), _step(m, bc)
+        Ls = []
+        for dp in (h, -h, h / 2, -h / 2, h / 4, -h / 4):
+            mm = copy.deepcopy(m)
+            mm.F[c] = p + dp
+            Lx, _, sx, bx, _ = oracle_episode(mm, q0[0], u[0], S, w, grad=False, qd0=qd0[0])
+            if bx or not np.array_equal(sx, sig0):
+                break
+            Ls.append(Lx)
+        if len(Ls) < 6:
+            continue
+        kept[i] = True
+        exact0[i] = all(L == L0 for L in Ls)
+        D1, D2, D4 = (Ls[0] - Ls[1]) / (2 * h), (Ls[2] - Ls[3]) / h, (Ls[4] - Ls[5]) / (h / 2)
+        R1[i], R2[i] = (4 * D2 - D1) / 3, (4 * D4 - D2) / 3
+    return {"R1": R1, "R2": R2, "kept": kept, "exact0": exact0, "sig0": sig0, "L0": L0}
+
+
+def sample_columns(cols, limit=70, n=40, seed=0, prefer=()):
+    """the columns a model's differences are taken on: all of them up to `limit`, else a seeded draw of n that holds every kind present — a
+    kind's own column drawn among `prefer` (column indices) where it has one there"""
+    if len(cols) <= limit:
+        return list(range(len(cols)))
+    rng = np.random.default_rng(seed)
+    kinds = [kind_of(bc) for bc in cols]
+    pick = []
+    for k in KINDS:
+        ks = [i for i in range(len(cols)) if kinds[i] == k]
+        ks = [i for i in ks if i in prefer] or ks
+        if ks:
+            pick.append(ks[int(rng.integers(len(ks)))])
+    rest = [i for i in rng.permutation(len(cols)) if i not in pick]
+    return sorted(pick + [int(i) for i in rest[:n - len(pick)]])
+
+
+def active_limit_columns(m, cols, states):
+    """indices of the limit columns of the dofs that are outside their limits at the end of some frame of the base run (states: [(q, qd)]): the
+    limit columns the loss can see.  A fact of the forward trajectory; no gradient is consulted."""
+    out = set()
+    for i, bc in enumerate(cols):
+        if bc[0] != "limit":
+            continue
+        base = bc[3] - ("lo", "hi", "k").index(bc[2])
+        k = (base - Bl.TSIM_DF_LIM_LO - int(m.I[Bl.TSIM_IH_FOFF_DOF])) // Bl.TSIM_DF_SIZE
+        lo, hi, kk = (float(m.F[base + j]) for j in range(3))
+        if kk > 0 and any((q[k] < lo and bc[2] != "hi") or (q[k] > hi and bc[2] != "lo") for q, _ in states):
+            out.add(i)
+    return out
+
+
+def oracle_body_check(name, T, tol=1e-15):
+    """One model, CPU only: the oracle's exact body adjoint (every group on) and the differences of its own forward pass at the same Newton
+    tolerance, on sample_columns().  Plain arrays (this runs in a spawned process): the gradient g, R1, R2, kept, exact0, differenced, the oracle's
+    results with the default mask and with the body groups on."""
+    m, q0, qd0, u, S = body_case(name, 1, T)
+    m = copy.deepcopy(m)
+    m.F[Bl.TSIM_FH_TOL] = tol
+    cols = m.body_param_columns()
+    w = loss_weights(m, u.shape[1], 1)
+    states = oracle_episode(m, q0[0], u[0], S, w, grad=False, qd0=qd0[0])[4]
+    only = sample_columns(cols, prefer=active_limit_columns(m, cols, states))
+    D = _differences(name, T, tol, set(only))
+    L, g, sig, bad, _ = oracle_episode(m, q0[0], u[0], S, w, qd0=qd0[0], groups=ALL)
+    L1, g1, sig1, bad1, _ = oracle_episode(m, q0[0], u[0], S, w, qd0=qd0[0])
+    assert bad == 0 and bad1 == 0 and L == L1 == D["L0"] and np.array_equal(sig, D["sig0"]), name
+    differenced = np.zeros(len(cols), bool)
+    differenced[only] = True
+    D.update(g=g, g_default=g1, differenced=differenced)
+    return D

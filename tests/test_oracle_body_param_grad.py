@@ -1,0 +1,178 @@
+"""The fp64 CPU oracle's exact body-parameter adjoint (oracle/tsim_oracle.cpp param_vjp_body, OracleSim.set_param_grad_groups: dL/d link mass,
+com, inertia; motor lo hi P D; limit lo hi k) against Richardson-extrapolated central differences of the oracle's own forward pass.  No GPU.
+
+The kernels' body groups are held to this adjoint (tests/test_gpu_body_param_grad_oracle.py), so here it is pinned to something that shares none
+of its derivative code.  Both sides run at Newton tol 1e-15, NOT 1e-13: the adjoint is the derivative of the CONVERGED dynamics, the differences
+are the derivative of whatever iterate the Newton loop stops at, and on a BDF2 sub-step an iterate accepted at 1e-13 is far enough from the root
+for the two to differ by 8e-4 (bdf2:ball_push; profiles/r12_body_param_grad_oracle.md).  At 1e-15 they agree to 2e-8 of the kind's scale, which
+test_bdf2_adjoint_equals_converged_differences keeps.
+
+The yardstick and its filter are those of tests/test_gpu_body_param_grad.py (body_param_util): a column is comparable if its six moved runs
+converge, keep the base's branch signature, and |R1 - R2| <= 1e-4 max(|R1|, 1e-5 S_kind).  Rule: |g - R1| <= 1e-3 max(|R1|, 1e-5 S_eff), the rule
+of tests/test_oracle_param_grad.py.  Models with more than 70 new columns are differenced on a seeded sample of 40 that holds every kind present."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import tactilesimulation_amd.model.blob as Bl      # noqa: E402
+from body_param_util import ALL, BODY, KINDS, LIMIT_CHAIN, MODELS, _step, body_case, kind_of, oracle_body_check      # noqa: E402
+from test_oracle_param_grad import loss_weights, oracle_episode      # noqa: E402
+
+TOL = 1e-15
+CASES = MODELS + [LIMIT_CHAIN]      # the yardstick's 17 models and the second limit model of the GPU file
+_RES = {}
+
+
+def _results():
+    """oracle_body_check of every model, side by side in spawned processes (at most 8), once per session"""
+    if not _RES:
+        import concurrent.futures
+        import multiprocessing
+        todo = sorted(CASES, key=lambda nt: -min(len(body_case(nt[0], 1, nt[1])[0].body_param_columns()), 70))
+        with concurrent.futures.ProcessPoolExecutor(max_workers=min(8, os.cpu_count() or 1), mp_context=multiprocessing.get_context("spawn")) as ex:
+            for nt, r in zip(todo, ex.map(oracle_body_check, *zip(*todo), [TOL] * len(todo))):
+                _RES[nt] = r
+    return _RES
+
+
+def _judged(name, T):
+    """the model's columns, kinds, comparable mask, S per kind and the floor scale S_eff per column (tests/test_gpu_body_param_grad.py yardstick())"""
+    D = _results()[(name, T)]
+    m = body_case(name, 1, T)[0]
+    cols = m.body_param_columns()
+    kinds = [kind_of(bc) for bc in cols]
+    kept, exact0, R1, R2 = D["kept"].copy(), D["exact0"].copy(), D["R1"], D["R2"]
+    for i, bc in enumerate(cols):      # lim_k of a dof without a limit: moving it switches a spring on, no derivative; the contract is exactly 0
+        if bc[0] == "limit" and bc[2] == "k" and m.F[bc[3]] == 0:
+            kept[i], exact0[i] = False, True
+    Sk = {k: max([abs(R1[i]) for i in range(len(cols)) if kinds[i] == k and kept[i]], default=0.0) for k in KINDS}
+    res = np.array([4 * np.spacing(abs(float(D["L0"]))) / _step(m, bc) for bc in cols])
+    comparable = np.array([bool(kept[i]) and abs(R1[i] - R2[i]) <= 1e-4 * max(abs(R1[i]), 1e-5 * Sk[kinds[i]]) for i in range(len(cols))])
+    Seff = np.array([max(Sk[kinds[i]], 1e5 * res[i]) for i in range(len(cols))])
+    return D, m, cols, kinds, comparable, exact0, Sk, Seff
+
+
+@pytest.mark.parametrize("name,T", CASES)
+def test_oracle_body_adjoint_equals_its_finite_differences(name, T):
+    D, m, cols, kinds, comparable, exact0, Sk, Seff = _judged(name, T)
+    g, R1 = D["g"], D["R1"]
+    n = int(D["differenced"].sum())
+    assert comparable.sum() >= 0.75 * n, (name, int(comparable.sum()), n)
+    other = np.setdiff1d(np.arange(g.size), [c for (_, _, _, c) in m.param_columns() + cols])
+    assert np.all(g[other] == 0), name
+    # the contact columns do not move with the body groups on; with the default mask the body columns stay 0
+    pc = [c for (_, _, _, c) in m.param_columns()]
+    bc_ = [c for (_, _, _, c) in cols]
+    assert np.array_equal(g[pc], D["g_default"][pc]) and np.all(D["g_default"][bc_] == 0), name
+    # a limit column of a dof without a limit, and a motor or limit column no moved run sees, is exactly 0
+    for i, bc in enumerate(cols):
+        if bc[0] == "limit" and m.F[bc[3] - (Bl.TSIM_DF_LIM_LO + ("lo", "hi", "k").index(bc[2])) + Bl.TSIM_DF_LIM_K] == 0:
+            assert g[bc[3]] == 0, (name, bc)
+        if exact0[i] and bc[0] != "link":
+            assert g[bc[3]] == 0, (name, bc)
+    err = [(abs(g[cols[i][3]] - R1[i]) / max(abs(R1[i]), 1e-5 * Seff[i]), kinds[i], cols[i][1:3]) for i in range(len(cols)) if comparable[i]]
+    print(name, "compared", len(err), "of", n, "max", max(err)[:2] if err else None)
+    assert max(e for e, _, _ in err) <= 1e-3, (name, sorted(err)[-5:])
+
+
+def test_differences_cover_every_kind():
+    """every kind has at least two comparable columns with |R1| >= 1e-3 S_kind, from two models"""
+    seen, count = {k: set() for k in KINDS}, {k: 0 for k in KINDS}
+    for name, T in MODELS:
+        D, m, cols, kinds, comparable, exact0, Sk, Seff = _judged(name, T)
+        for i in range(len(cols)):
+            if comparable[i] and Sk[kinds[i]] > 0 and abs(D["R1"][i]) >= 1e-3 * Sk[kinds[i]]:
+                seen[kinds[i]].add(name)
+                count[kinds[i]] += 1
+    print({k: (count[k], sorted(seen[k])) for k in KINDS})
+    for k in KINDS:
+        assert count[k] >= 2 and len(seen[k]) >= 2, (k, count[k], sorted(seen[k]))
+
+
+@pytest.mark.parametrize("name,T", [("bdf2:ball_push", 3), ("bdf2:tactile_pad", 3)])
+def test_bdf2_adjoint_equals_converged_differences(name, T):
+    """The regression for "the BDF2 adjoint deviates from finite differences by 8e-4": it does not.  At tol 1e-13 the Newton loop of these models
+    stops at an iterate whose derivative is not the root's (the differences moved, not the adjoint: measured 3.0e-4 S_kind at 1e-13 on
+    bdf2:ball_push, 1.7e-9 at 1e-15; bdf2:tactile_pad 1.9e-8).  Asserted at 1e-15: max |g - R1| / S_kind <= 1e-6."""
+    D, m, cols, kinds, comparable, exact0, Sk, Seff = _judged(name, T)
+    assert int(m.I[Bl.TSIM_IH_INTEGRATOR]) == 2
+    # by S_kind itself; a kind none of whose columns the loss sees (S_kind = 0: the position motor's lo / hi, ...) has no scale, there by what
+    # the differences resolve (S_eff of _judged)
+    err = [(abs(D["g"][cols[i][3]] - D["R1"][i]) / (Sk[kinds[i]] or Seff[i]), kinds[i]) for i in range(len(cols)) if comparable[i]]
+    print(name, "compared", len(err), "max |g - R1| / S_kind", max(err))
+    assert len(err) >= 0.75 * len(cols) and max(e for e, _ in err) <= 1e-6, sorted(err)[-5:]
+
+
+def test_body_groups_leave_every_other_result_unchanged():
+    """default mask: the numbers the oracle returned before; body groups on: dL/du and the carried adjoint bit for bit, the columns of a group
+    that is off untouched"""
+    from oracle.oracle import OracleSim
+    m, q0, qd0, u, S = body_case("limit_push", 1, 4)
+    T = u.shape[1]
+    w = loss_weights(m, T)
+    res = {}
+    for groups in (None, ("contact",), ALL, BODY, ("inertial",)):
+        o = OracleSim(m)
+        o.reset(q0[0], record=True)
+        for t in range(T):
+            o.forward(u[0, t], S)
+        buf = np.zeros(o._L.orc_table_size(o._h))
+        o.set_param_grad(buf)
+        if groups is not None:
+            o.set_param_grad_groups(groups)
+        du = []
+        for t in reversed(range(T)):
+            dq = np.zeros((S, m.ndof_r)); dq[-1] = w[0][t]
+            du.append(o.backward_steps(S, dq, None, None))
+        res[groups] = (np.array(du), o.adjoint(), buf)
+    pc = [c for (_, _, _, c) in m.param_columns()]
+    link = [c for (k, _, _, c) in m.body_param_columns() if k == "link"]
+    rest = [c for (k, _, _, c) in m.body_param_columns() if k != "link"]
+    ref = res[None]
+    for groups, r in res.items():
+        assert np.array_equal(ref[0], r[0]) and all(np.array_equal(a, b) for a, b in zip(ref[1], r[1])), groups
+    assert np.array_equal(ref[2], res[("contact",)][2]) and np.all(ref[2][link + rest] == 0) and np.abs(ref[2][pc]).max() > 0
+    assert np.array_equal(res[ALL][2][pc], ref[2][pc]) and np.all(res[BODY][2][pc] == 0)
+    assert np.array_equal(res[ALL][2][link + rest], res[BODY][2][link + rest]) and np.abs(res[ALL][2][rest]).max() > 0
+    assert np.array_equal(res[("inertial",)][2][link], res[ALL][2][link]) and np.all(res[("inertial",)][2][rest] == 0)
+    assert o._L.orc_set_param_grad_groups(o._h, 16) != 0 and o._L.orc_set_param_grad_groups(o._h, -1) != 0
+    with pytest.raises(KeyError):
+        o.set_param_grad_groups(("geometry",))
+
+
+@pytest.mark.parametrize("name,T", [("pusher", 3), ("bdf2:ball_push", 3), ("limit_push", 4)])
+def test_default_mask_returns_what_the_oracle_returned_before_the_body_groups(name, T):
+    """tests/golden/oracle_default_mask.npz: forward states and outputs, the contact columns of the table gradient, dL/du and the carried adjoint
+    as a build of the oracle's source BEFORE the body groups (kinematics and residual without the Dual tables of links, motors and limits) returned
+    them.  On the host that wrote the fixture this build returns the same bits (printed).  Asserted to 1e-9: another host's C library may
+    round sin / cos differently in the last place (1e-16), and a short episode of stiff contact (kn up to 1e5) carries that to the results with
+    a condition of that order at the most; a slip in the refactored reads would show at 1e-3 and above."""
+    from oracle.oracle import OracleSim
+    z = np.load(os.path.join(HERE, "golden", "oracle_default_mask.npz"))
+    m, q0, qd0, u, S = body_case(name, 1, T)
+    w = loss_weights(m, u.shape[1], 1)
+    o = OracleSim(m)
+    o.reset(q0[0], qd0[0], record=True)
+    fwd = []
+    for t in range(u.shape[1]):
+        o.forward(u[0, t], S)
+        fwd += list(o.state()) + list(o.outputs())
+    g = np.zeros(o._L.orc_table_size(o._h))
+    o.set_param_grad(g)
+    du = []
+    for t in reversed(range(u.shape[1])):
+        dq = np.zeros((S, m.ndof_r)); dq[-1] = w[0][t]
+        dv = np.zeros((S, m.ndof_var)); dv[-1] = w[1][t]
+        dt = np.zeros((S, m.ndof_tactile)); dt[-1] = w[2][t]
+        du.append(o.backward_steps(S, dq, dv if m.ndof_var else None, dt if m.ndof_tactile else None))
+    got = {"forward": np.concatenate([np.ravel(x) for x in fwd]), "table_grad": g, "du": np.concatenate([np.ravel(d) for d in du]),
+           "adjoint": np.concatenate([np.ravel(x) for x in o.adjoint()])}
+    for k, v in got.items():
+        ref = z["%s__%s" % (name.replace(":", "_"), k)]
+        assert ref.shape == v.shape and np.abs(ref).max() > 0, k
+        np.testing.assert_allclose(v, ref, rtol=1e-9, atol=1e-9 * np.abs(ref).max(), err_msg="%s %s" % (name, k))
+        print(name, k, "equal bit for bit" if np.array_equal(v, ref) else "max abs difference %.3g" % np.abs(v - ref).max())

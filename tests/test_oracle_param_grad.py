@@ -85,9 +85,10 @@ def kind_of(pc):
     return "%s %s" % (pc[0], pc[2])
 
 
-def oracle_episode(m, q0, u, S, w, grad=True, tac_mask=None, qd0=None):
+def oracle_episode(m, q0, u, S, w, grad=True, tac_mask=None, qd0=None, groups=None):
     """One environment on the fp64 oracle from (q0, qd0): the frames of u [T, nu], the loss sum_t wq[t].q_t + wv[t].var_t + wt[k].tac_t at each frame's end
     (tac only at the frames tac_mask keeps, seeded by their own rows of wt), and its adjoint frame by frame with the table gradient on.
+    groups: OracleSim.set_param_grad_groups' names (None: the default, the contact columns).
     Returns (loss, table gradient [table_size] or None, signatures [T S, 2], non-converged sub-steps, frame states [(q, qd)])."""
     from oracle.oracle import OracleSim
     o = OracleSim(m)
@@ -108,6 +109,8 @@ def oracle_episode(m, q0, u, S, w, grad=True, tac_mask=None, qd0=None):
     if grad:
         g = np.zeros(o._L.orc_table_size(o._h))
         o.set_param_grad(g)
+        if groups is not None:
+            o.set_param_grad_groups(groups)
         for t in reversed(range(T)):
             dq = np.zeros((S, nr)); dq[-1] = wq[t]
             dv = np.zeros((S, m.ndof_var)); dv[-1] = wv[t]

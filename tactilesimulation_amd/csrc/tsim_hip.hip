@@ -460,10 +460,10 @@ struct tsim_batch {
   std::vector<void*> retired;       // per-frame pose records replaced by larger ones while a captured graph may still name them (launch_forward)
   long long* bwd_stamps = nullptr;  // diagnostics (tsim_debug_stamps)
   // tsim_set_param_grad: the caller's table gradient [B][nfrec] (null: off), the adjoint solutions z [cap][B][nr] the adjoint launch saves for the
-  // parameter pass, and that pass's partial sums [pg_chunks][B][ts_pg_count] (both allocated when the gradient is first asked for)
+  // parameter passes, and the contact pass's partial sums [pg_chunks][B][ts_pg_count] (pg_alloc: both when the gradient is first asked for)
   void* dLdp = nullptr; void* zbuf = nullptr; void* pgpart = nullptr; int pg_chunks = 0;
   // tsim_set_param_grad_groups: which groups of columns a launch adds to (TSIM_PG_*), and the body pass's partial sums
-  // [pg_chunks][B][ts_pgb_count] (allocated when a body group is first asked for)
+  // [pg_chunks][B][ts_pgb_count] (pg_alloc: once a body group is on and the gradient is asked for)
   int pg_groups = TS_PG_CONTACT; void* pgbpart = nullptr;
   // tsim_kernel_timing: HIP events around every launch of the simulation kernels, on the stream they are launched on
   int kt_on = 0;
@@ -900,55 +900,53 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   return 0;
 }
 
-// Chunks of sub-steps per environment in the parameter pass: enough (environment, chunk) slots for about four wavefronts per SIMD at four
-// environments per wavefront, at most one chunk per sub-step.  A function of the batch alone, so that the partial-sum buffer is sized once.
-static int pg_chunks_for(const tsim_batch* b, int n) {
+// The parameter passes' slots.  Chunks of sub-steps per environment: enough (environment, chunk) slots for about four wavefronts per SIMD at four
+// environments per wavefront, at most one chunk per sub-step (most), then chunks of equal length and none of them empty (nchunk x chunk_len).
+// most is a function of the batch alone for n = the tape's capacity, so that the partial-sum buffers are sized once (pg_alloc).
+struct PgLayout { int nchunk, chunk_len, most; };
+static PgLayout pg_layout(const tsim_batch* b, int n) {
   const int want = (int)std::max<long long>(1, (16LL * b->n_simd + b->B - 1) / b->B);
-  return std::max(1, std::min(n, want));
+  const int most = std::max(1, std::min(n, want)), chunk_len = (n + most - 1) / most;
+  return {(n + chunk_len - 1) / chunk_len, chunk_len, most};
 }
-// the parameter pass of an adjoint launch (tsim_set_param_grad): k_param_grad over the sub-steps the launch just undid, then the fixed-order
-// reduction into the caller's buffer
+// A parameter pass of an adjoint launch (tsim_set_param_grad): the pass's kernel (TsLaunch::run picks it by the type of p, whose own fields the
+// caller has set) over the sub-steps the launch just undid, then the fixed-order reduction of its partial sums into the caller's buffer
+template <class R, class Args>
+static int launch_param_pass(tsim_batch* b, TsKernel kernel, const char* name, const char* no_part, Args& p, int n, void* part, const PgSeg (&seg)[3], hipStream_t st) {
+  const PgLayout lay = pg_layout(b, n);
+  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = n; p.t_end = b->t_cur;
+  p.tape = (const R*)b->tape; p.z = (const R*)b->zbuf; p.nchunk = lay.nchunk; p.chunk_len = lay.chunk_len;
+  p.P = seg[0].count + seg[1].count + seg[2].count; p.part = (R*)part; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
+  if (!part || p.nchunk > b->pg_chunks) return fail(no_part);
+  TsPlan plan = ts_plan(b, kernel, false, 0);
+  plan.grid *= p.nchunk;
+  if (!TsLaunch<void, false, R>::run(plan, st, p)) return fail(std::string("no ") + name + " instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  ts_param_reduce_launch(PgReduceArgs<R>{(const R*)part, p.nchunk, b->B, p.P, (R*)b->dLdp, b->nfrec, {seg[0], seg[1], seg[2]}}, st);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// the contact groups: [pair kn kt mu kd], [sensor kn kt mu kd], [dof damping] (ts_pg_count)
 template <class R>
 static int launch_param_grad(tsim_batch* b, int n, int seed_stride, int frames, const int32_t* tac_slot, const void* df_dtac, hipStream_t st) {
-  const int npair = b->I[TSIM_IH_NPAIR], nsensor = b->I[TSIM_IH_NSENSOR];
   PgArgs<R> p;
-  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = n; p.t_end = b->t_cur;
-  p.seed_stride = seed_stride; p.frames = frames; p.tac_slot = tac_slot; p.tape = (const R*)b->tape; p.z = (const R*)b->zbuf;
-  p.df_dtac = (const R*)df_dtac; p.nchunk = pg_chunks_for(b, n); p.chunk_len = (n + p.nchunk - 1) / p.nchunk;
-  p.nchunk = (n + p.chunk_len - 1) / p.chunk_len;          // (no empty chunk)
-  p.P = ts_pg_count(npair, nsensor, b->nr); p.part = (R*)b->pgpart; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
-  if (p.nchunk > b->pg_chunks) return fail("param_grad: partial-sum buffer too small");
-  TsPlan plan = ts_plan(b, TS_K_PARAM_GRAD, false, 0);
-  plan.grid *= p.nchunk;
-  if (!TsLaunch<void, false, R>::run(plan, st, p)) return fail("no k_param_grad instantiation for the launch plan");
-  HIPCHK(hipGetLastError());
-  PgReduceArgs<R> r{(const R*)b->pgpart, p.nchunk, b->B, p.P, (R*)b->dLdp, b->nfrec, npair, nsensor, b->nr,
-                    b->I[TSIM_IH_FOFF_PAIR], b->I[TSIM_IH_FOFF_SENSOR], b->I[TSIM_IH_FOFF_DOF]};
-  ts_param_reduce_launch(r, st);
-  HIPCHK(hipGetLastError());
-  return 0;
+  p.seed_stride = seed_stride; p.frames = frames; p.tac_slot = tac_slot; p.df_dtac = (const R*)df_dtac;
+  const PgSeg seg[3] = {{4 * b->I[TSIM_IH_NPAIR], 4, TSIM_PF_SIZE, b->I[TSIM_IH_FOFF_PAIR] + TSIM_PF_KN, 1},
+                        {4 * b->I[TSIM_IH_NSENSOR], 4, TSIM_SF_SIZE, b->I[TSIM_IH_FOFF_SENSOR] + TSIM_SF_KN, 1},
+                        {b->nr, 1, TSIM_DF_SIZE, b->I[TSIM_IH_FOFF_DOF] + TSIM_DF_DAMPING, 1}};
+  return launch_param_pass<R>(b, TS_K_PARAM_GRAD, "k_param_grad", "param_grad: partial-sum buffer too small", p, n, b->pgpart, seg, st);
 }
-
-// ... and the body groups' pass (tsim_set_param_grad_groups): k_param_grad_body over the same sub-steps and chunks, then its reduction
+// ... and the body groups (tsim_set_param_grad_groups): [link mass com inertia], [motor lo hi P D], [dof lim_lo lim_hi lim_k] (ts_pgb_count);
+// only the groups that are on are evaluated and added
 template <class R>
 static int launch_param_grad_body(tsim_batch* b, int n, hipStream_t st) {
-  const int nl = b->I[TSIM_IH_NL];
   PgBodyArgs<R> p;
-  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = n; p.t_end = b->t_cur;
-  p.tape = (const R*)b->tape; p.z = (const R*)b->zbuf;
-  p.nchunk = pg_chunks_for(b, n); p.chunk_len = (n + p.nchunk - 1) / p.nchunk;
-  p.nchunk = (n + p.chunk_len - 1) / p.chunk_len;          // (no empty chunk)
-  p.P = ts_pgb_count(nl, b->nu, b->nr); p.part = (R*)b->pgbpart; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k; p.groups = b->pg_groups;
-  if (!b->pgbpart || p.nchunk > b->pg_chunks) return fail("param_grad: the body groups' partial-sum buffer is missing or too small");
-  TsPlan plan = ts_plan(b, TS_K_PARAM_GRAD_BODY, false, 0);
-  plan.grid *= p.nchunk;
-  if (!TsLaunch<void, false, R>::run(plan, st, p)) return fail("no k_param_grad_body instantiation for the launch plan");
-  HIPCHK(hipGetLastError());
-  PgBodyReduceArgs<R> r{(const R*)b->pgbpart, p.nchunk, b->B, p.P, (R*)b->dLdp, b->nfrec, nl, b->nu, b->nr,
-                        b->I[TSIM_IH_FOFF_LINK], b->I[TSIM_IH_FOFF_MOTOR], b->I[TSIM_IH_FOFF_DOF], b->pg_groups};
-  ts_param_reduce_body_launch(r, st);
-  HIPCHK(hipGetLastError());
-  return 0;
+  p.groups = b->pg_groups;
+  const PgSeg seg[3] = {{10 * b->I[TSIM_IH_NL], 10, TSIM_LF_SIZE, b->I[TSIM_IH_FOFF_LINK] + TSIM_LF_MASS, b->pg_groups & TS_PG_INERTIAL},
+                        {4 * b->nu, 4, 4, b->I[TSIM_IH_FOFF_MOTOR], b->pg_groups & TS_PG_MOTOR},      // TSIM_MF_SIZE = 4: lo hi P D
+                        {3 * b->nr, 3, TSIM_DF_SIZE, b->I[TSIM_IH_FOFF_DOF] + TSIM_DF_LIM_LO, b->pg_groups & TS_PG_LIMIT}};
+  return launch_param_pass<R>(b, TS_K_PARAM_GRAD_BODY, "k_param_grad_body", "param_grad: the body groups' partial-sum buffer is missing or too small", p, n,
+                              b->pgbpart, seg, st);
 }
 
 template <class R>
@@ -1199,12 +1197,24 @@ int tsim_set_env_tables(tsim_batch* b, const void* tables, void* stream) {
 }
 int tsim_table_size(const tsim_batch* b) { return b->nfrec; }
 
-// the body pass's partial sums, once a body group is on and the gradient is asked for (the default mask never gets here)
-static int pg_body_alloc(tsim_batch* b) {
-  if (b->pgbpart || !(b->pg_groups & ~TS_PG_CONTACT)) return 0;
+// What the parameter passes need on the device, once a gradient buffer is asked for: z of every taped sub-step and the contact pass's partial sums,
+// and, once a body group is on as well, the body pass's partial sums (the default mask never allocates those).  What is there already stays.
+static int pg_alloc(tsim_batch* b) {
+  const bool body = (b->pg_groups & ~TS_PG_CONTACT) != 0;
+  if (b->zbuf && b->pgpart && (b->pgbpart || !body)) return 0;
   TS_DEVICE(b);
-  const size_t pb = (size_t)pg_chunks_for(b, b->cap) * b->B * ts_pgb_count(b->I[TSIM_IH_NL], b->nu, b->nr) * b->esz;
-  if (hipMalloc(&b->pgbpart, std::max<size_t>(pb, 8)) != hipSuccess) { (void)hipGetLastError(); b->pgbpart = nullptr; return fail("set_param_grad_groups: hipMalloc failed"); }
+  const int chunks = pg_layout(b, b->cap).most;
+  auto get = [&](void** p, size_t reals) {
+    if (*p || hipMalloc(p, std::max<size_t>(reals * b->B * b->esz, 8)) == hipSuccess) return true;
+    (void)hipGetLastError(); *p = nullptr;
+    return false;
+  };
+  if (body && !get(&b->pgbpart, (size_t)chunks * ts_pgb_count(b->I[TSIM_IH_NL], b->nu, b->nr))) return fail("set_param_grad_groups: hipMalloc failed");
+  if (!get(&b->zbuf, (size_t)b->cap * b->nr) || !get(&b->pgpart, (size_t)chunks * ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr))) {
+    (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); b->zbuf = nullptr; b->pgpart = nullptr;
+    return fail("set_param_grad: hipMalloc failed");
+  }
+  b->pg_chunks = chunks;
   return 0;
 }
 
@@ -1213,24 +1223,13 @@ int tsim_set_param_grad_groups(tsim_batch* b, int mask) {
   if (mask < 0 || (mask & ~(TS_PG_CONTACT | TS_PG_INERTIAL | TS_PG_MOTOR | TS_PG_LIMIT))) return fail("set_param_grad_groups: unknown group in mask " + std::to_string(mask));
   const int before = b->pg_groups;
   b->pg_groups = mask;
-  if (b->dLdp && pg_body_alloc(b)) { b->pg_groups = before; return 1; }
+  if (b->dLdp && pg_alloc(b)) { b->pg_groups = before; return 1; }
   return 0;
 }
 int tsim_get_param_grad_groups(const tsim_batch* b) { return b ? b->pg_groups : -1; }
 
 int tsim_set_param_grad(tsim_batch* b, void* dL_dtables) {
-  if (dL_dtables && pg_body_alloc(b)) return 1;
-  if (dL_dtables && (!b->zbuf || !b->pgpart)) {
-    TS_DEVICE(b);
-    const int chunks = pg_chunks_for(b, b->cap);
-    const size_t zb = (size_t)b->cap * b->B * b->nr * b->esz;
-    const size_t pb = (size_t)chunks * b->B * ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr) * b->esz;
-    if (hipMalloc(&b->zbuf, std::max<size_t>(zb, 8)) != hipSuccess || hipMalloc(&b->pgpart, std::max<size_t>(pb, 8)) != hipSuccess) {
-      (void)hipGetLastError(); (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); b->zbuf = nullptr; b->pgpart = nullptr;
-      return fail("set_param_grad: hipMalloc failed");
-    }
-    b->pg_chunks = chunks;
-  }
+  if (dL_dtables && pg_alloc(b)) return 1;
   b->dLdp = dL_dtables;
   return 0;
 }

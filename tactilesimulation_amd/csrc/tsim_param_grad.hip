@@ -3,11 +3,13 @@
 //   k_param_grad    slot = (environment, chunk of sub-steps), 16 / 32 / 64 lanes as the adjoint launch: per sub-step a value-only link sweep of the
 //                   taped state, then per dynamics pair lanes = contact points (the wrench's parameter derivatives dotted with the z-weighted
 //                   motion of the pair, one reduction of 4 numbers), the damping term, and at seeded sub-steps the tactile term over the taxels;
-//   k_param_reduce  one thread per (environment, parameter): the chunks' partial sums added in chunk order into the caller's table gradient.
+//   k_param_reduce  one thread per (environment, parameter): the chunks' partial sums added in chunk order into the caller's table gradient
+//                   (the body pass's reduction too: the columns are an argument).
+// The slot mapping, the sub-step header and the taped-state load are tsim_param_pass.h's, shared with k_param_grad_body.
 // Built like the generic kernels (tsim_hip.hip): no fast-math flags, the fp64 instantiation follows the fp64 adjoint to round-off.
 #include <hip/hip_runtime.h>
 #include "tsim_kernels.h"
-#include "tsim_param_grad.h"
+#include "tsim_param_pass.h"
 #include "tsim_launch.h"
 
 // Adds v[k] to out[i0 + k], k < 4.  Entry i of a slot's partial row is always touched by lane i % LPE of the slot — zeroing included — so every
@@ -21,33 +23,24 @@ template <class R, bool EXPJ, int LPE>
 __global__ void __launch_bounds__(TS_WAVE) k_param_grad(PgArgs<R> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   R* lds = reinterpret_cast<R*>(smem_raw);
-  constexpr int NS = TS_WAVE / LPE;
-  const int slot = threadIdx.x / LPE, lane = threadIdx.x % LPE;
-  // block -> (chunk, NS neighbouring environments): every slot of a wavefront walks the same sub-steps (the loop below has barriers)
-  const int bpc = (a.B + NS - 1) / NS, chunk = (int)blockIdx.x / bpc;
-  const int e_ = ((int)blockIdx.x - chunk * bpc) * NS + slot;
+  const int lane = threadIdx.x % LPE, chunk = pg_chunk<LPE>(a), e_ = pg_slot_env<LPE>(a, chunk);      // (the scaffold: tsim_param_pass.h)
   const bool valid = e_ < a.B;                                 // an idle slot of a chunk's last block repeats the last environment and stores nothing
   const int env = min(e_, a.B - 1);
-  Ctx<R> c; ctx_init<R>(c, a.I, a.F, lds, NS, slot, lane, LPE, a.stage_cpt != 0, a.Fenv ? a.Fenv + (size_t)env * a.fstride : nullptr);
+  Ctx<R> c; pg_ctx<LPE>(a, lds, c, lane, env);
   const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R), a.tk);
   const int npair = c.npair, nsensor = c.nsensor, ntac3 = 3 * c.ntax;
-  init_world(c, lane, LPE);
-  R* out = a.part + ((size_t)chunk * a.B + env) * a.P;
+  R* out = pg_row(a, chunk, env);
   const int idamp = 4 * npair + 4 * nsensor;
   if (valid) for (int i = lane; i < idamp; i += LPE) out[i] = R(0);
   const bool bdf2_model = ts_u(c.I[TSIM_IH_INTEGRATOR]) == 2;
   R gdamp = R(0);                                             // this lane's dof: -sum z qd1 / ca
   const int j0 = chunk * a.chunk_len, j1 = min(a.n, j0 + a.chunk_len);
   for (int j = j0; j < j1; ++j) {
-    const int t = a.t_end - (a.n - 1 - j);
-    const bool bdf2 = bdf2_model && t >= 2;                   // (k_backward's choice of the sub-step's integrator)
-    const R ca = bdf2 ? R(2.25) / (c.h * c.h) : R(1) / (c.h * c.h);
-    const R* rec = a.tape + ((size_t)t * a.B + env) * REC;
+    const int t = pg_t(a, j);
+    const R ca = pg_ca(c, bdf2_model && t >= 2);
+    const R* rec = pg_rec(a, t, env, REC);
     TS_SYNC();
-    if (lane < nr) {
-      c.qD[lane] = rec_q(rec)[lane]; c.q[lane] = (R)c.qD[lane]; c.qd[lane] = rec[rec_qd<R>(nr) + lane]; c.qa[lane] = R(0);
-      c.z[lane] = a.z[((size_t)(t - 1) * a.B + env) * nr + lane];
-    }
+    if (lane < nr) { pg_load_state(a, c, rec, t, env, nr, lane); c.qa[lane] = R(0); }
     TS_SYNC();
     phase1<R, false, EXPJ>(c, lane, R(0), R(0), R(0));         // link poses, twists and joint columns W of the taped state
     TS_SYNC();
@@ -154,21 +147,22 @@ __global__ void __launch_bounds__(TS_WAVE) k_param_grad(PgArgs<R> a) {
   if (valid && lane < nr) out[idamp + lane] = gdamp;
 }
 
+// Either pass's reduction (PgReduceArgs: the segments of the pass's compact vector and the columns they belong to)
 template <class R>
 __global__ void __launch_bounds__(256) k_param_reduce(PgReduceArgs<R> a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.B * a.P) return;
   const int env = i / a.P, p = i - env * a.P;
+  PgSeg g = a.seg[0];
+  int q = p;
+  if (q >= g.count) { q -= g.count; g = a.seg[1]; if (q >= g.count) { q -= g.count; g = a.seg[2]; } }
+  if (!g.on) return;
   R s = R(0);
   for (int k = 0; k < a.nchunk; ++k) s += a.part[((size_t)k * a.B + env) * a.P + p];      // fixed order: bit-identical from run to run
-  int col;
-  if (p < 4 * a.npair) col = a.foff_pair + (p >> 2) * TSIM_PF_SIZE + TSIM_PF_KN + (p & 3);
-  else if (p < 4 * a.npair + 4 * a.nsensor) { const int q = p - 4 * a.npair; col = a.foff_sensor + (q >> 2) * TSIM_SF_SIZE + TSIM_SF_KN + (q & 3); }
-  else col = a.foff_dof + (p - 4 * a.npair - 4 * a.nsensor) * TSIM_DF_SIZE + TSIM_DF_DAMPING;
-  a.out[(size_t)env * a.stride + col] += s;
+  a.out[(size_t)env * a.stride + g.col0 + (q / g.per) * g.rec + q % g.per] += s;
 }
 
-// the launch itself: tsim_launch.h, as every simulation kernel's (the plan: tsim_hip.hip launch_param_grad)
+// the launch itself: tsim_launch.h, as every simulation kernel's (the plan: tsim_hip.hip launch_param_pass)
 template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const PgArgs<float>&);
 template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PgArgs<double>&);
 void ts_param_reduce_launch(const PgReduceArgs<float>& a, hipStream_t st) {

@@ -1,15 +1,15 @@
 // tsim_param_grad_body.hip — the body groups of the parameter gradient (include/tsim.h tsim_set_param_grad_groups: link inertia, motors, limits; the
 // math: DESIGN.md §4 "Parameter gradient: body groups").  Runs after k_backward_z like the contact pass (tsim_param_grad.hip), only when a body group
-// is asked for, with the same slots — (environment, chunk of sub-steps), 16 / 32 / 64 lanes as the adjoint launch — and the same kind of reduction:
+// is asked for, on the contact pass's scaffold (tsim_param_pass.h: the slots — (environment, chunk of sub-steps), 16 / 32 / 64 lanes as the adjoint
+// launch —, the sub-step header, the taped-state load) and with its reduction (k_param_reduce, tsim_param_grad.hip, given this pass's columns):
 //   k_param_grad_body    per sub-step a value-only link sweep of the taped state WITH its discrete accelerations (the contact pass evaluates with
 //                        none); lanes = (link, component) form Z_i = sum of z_j W_j over the dofs above link i, lanes = (link, parameter) the ten
 //                        derivatives of Z_i . F_i; lanes = motors and lanes = dofs the joint-space terms;
-//   k_param_reduce_body  one thread per (environment, parameter): the chunks' partial sums added in chunk order, into the enabled groups' columns.
 // A translation unit of its own: k_param_grad stays, instruction for instruction, the kernel it was (adding a kernel to its unit moved its fp64
 // instantiations by a few hundred code bytes).  Built like the generic kernels: no fast-math flags.
 #include <hip/hip_runtime.h>
 #include "tsim_kernels.h"
-#include "tsim_param_grad.h"
+#include "tsim_param_pass.h"
 #include "tsim_launch.h"
 
 // ================================================================================================ body groups
@@ -39,16 +39,12 @@ template <class R, bool EXPJ, int LPE>
 __global__ void __launch_bounds__(TS_WAVE) k_param_grad_body(PgBodyArgs<R> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   R* lds = reinterpret_cast<R*>(smem_raw);
-  constexpr int NS = TS_WAVE / LPE;
-  const int slot = threadIdx.x / LPE, lane = threadIdx.x % LPE;
-  const int bpc = (a.B + NS - 1) / NS, chunk = (int)blockIdx.x / bpc;      // block -> (chunk, NS neighbouring environments), as k_param_grad
-  const int e_ = ((int)blockIdx.x - chunk * bpc) * NS + slot;
+  const int lane = threadIdx.x % LPE, chunk = pg_chunk<LPE>(a), e_ = pg_slot_env<LPE>(a, chunk);      // (the scaffold: tsim_param_pass.h)
   const bool valid = e_ < a.B;
   const int env = min(e_, a.B - 1);
-  Ctx<R> c; ctx_init<R>(c, a.I, a.F, lds, NS, slot, lane, LPE, a.stage_cpt != 0, a.Fenv ? a.Fenv + (size_t)env * a.fstride : nullptr);
+  Ctx<R> c; pg_ctx<LPE>(a, lds, c, lane, env);
   const int nr = c.nr, nu = c.nu, nl = c.nl, REC = ts_rec(nr, nu, (int)sizeof(R), a.tk);
   const int oqd = rec_qd<R>(nr), ou = rec_u<R>(nr);
-  init_world(c, lane, LPE);
   // the tangent records are not used by a value-only sweep: Z_i (6 per link) and the links' running sums (10 per link) live there
   // (16 (nl + 1) reals of the (nl + 1) nr DT_SIZE the slot has)
   R* Zl = c.DT;
@@ -61,14 +57,14 @@ __global__ void __launch_bounds__(TS_WAVE) k_param_grad_body(PgBodyArgs<R> a) {
   const bool bdf2_model = ts_u(c.I[TSIM_IH_INTEGRATOR]) == 2;
   const int j0 = chunk * a.chunk_len, j1 = min(a.n, j0 + a.chunk_len);
   for (int j = j0; j < j1; ++j) {
-    const int t = a.t_end - (a.n - 1 - j);
-    const bool bdf2 = bdf2_model && t >= 2;                   // (k_backward's choice of the sub-step's integrator)
-    const R ca = bdf2 ? R(2.25) / (c.h * c.h) : R(1) / (c.h * c.h);
-    const R* rec = a.tape + ((size_t)t * a.B + env) * REC;
-    const R* rec0 = a.tape + ((size_t)(t - 1) * a.B + env) * REC;
+    const int t = pg_t(a, j);
+    const bool bdf2 = bdf2_model && t >= 2;
+    const R ca = pg_ca(c, bdf2);
+    const R* rec = pg_rec(a, t, env, REC);
+    const R* rec0 = pg_rec(a, t - 1, env, REC);
     TS_SYNC();
     if (lane < nr) {
-      c.qD[lane] = rec_q(rec)[lane]; c.q[lane] = (R)c.qD[lane]; c.qd[lane] = rec[oqd + lane];
+      pg_load_state(a, c, rec, t, env, nr, lane);
       // the sub-step's discrete acceleration.  fp64: as k_backward forms it, from the taped velocities.  fp32: the taped velocities are rounded to
       // 24 bits and their difference over h is what the inertial derivatives are proportional to (6e-8 |qd| / h of error, 1e-4 of a gentle
       // acceleration), while the taped POSITIONS are double: there the velocities are formed again from them, as the integrator defines them
@@ -87,7 +83,6 @@ __global__ void __launch_bounds__(TS_WAVE) k_param_grad_body(PgBodyArgs<R> a) {
         qa = bdf2 ? (3.0 * vel(t) - 4.0 * vel(t - 1) + vel(t - 2)) / (2.0 * hd) : (vel(t) - vel(t - 1)) / hd;
       }
       c.qa[lane] = (R)qa;
-      c.z[lane] = a.z[((size_t)(t - 1) * a.B + env) * nr + lane];
     }
     if (lane < nu) c.u[lane] = rec[ou + lane];
     TS_SYNC();
@@ -143,7 +138,7 @@ __global__ void __launch_bounds__(TS_WAVE) k_param_grad_body(PgBodyArgs<R> a) {
     }
   }
   TS_SYNC();
-  R* out = a.part + ((size_t)chunk * a.B + env) * a.P;
+  R* out = pg_row(a, chunk, env);
   if (valid) {
     for (int t0 = 0; t0 < nlt; t0 += LPE) if (t0 + lane < nlt) out[t0 + lane] = acc[t0 + lane];
     if (lane < nu) {
@@ -157,27 +152,6 @@ __global__ void __launch_bounds__(TS_WAVE) k_param_grad_body(PgBodyArgs<R> a) {
   }
 }
 
-template <class R>
-__global__ void __launch_bounds__(256) k_param_reduce_body(PgBodyReduceArgs<R> a) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.B * a.P) return;
-  const int env = i / a.P, p = i - env * a.P;
-  int col, group;
-  if (p < 10 * a.nl) { col = a.foff_link + (p / 10) * TSIM_LF_SIZE + TSIM_LF_MASS + p % 10; group = TS_PG_INERTIAL; }      // mass, com, inertia: contiguous
-  else if (p < 10 * a.nl + 4 * a.nu) { col = a.foff_motor + (p - 10 * a.nl); group = TS_PG_MOTOR; }                        // TSIM_MF_SIZE = 4: lo hi P D
-  else { const int q = p - 10 * a.nl - 4 * a.nu; col = a.foff_dof + (q / 3) * TSIM_DF_SIZE + TSIM_DF_LIM_LO + q % 3; group = TS_PG_LIMIT; }
-  if (!(a.groups & group)) return;
-  R s = R(0);
-  for (int k = 0; k < a.nchunk; ++k) s += a.part[((size_t)k * a.B + env) * a.P + p];      // fixed order: bit-identical from run to run
-  a.out[(size_t)env * a.stride + col] += s;
-}
-
-// the launch itself: tsim_launch.h, as every simulation kernel's (the plan: tsim_hip.hip launch_param_grad_body)
+// the launch itself: tsim_launch.h, as every simulation kernel's (the plan: tsim_hip.hip launch_param_pass)
 template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const PgBodyArgs<float>&);
 template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PgBodyArgs<double>&);
-void ts_param_reduce_body_launch(const PgBodyReduceArgs<float>& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_param_reduce_body<float>, dim3((unsigned)((a.B * a.P + 255) / 256)), dim3(256), 0, st, a);
-}
-void ts_param_reduce_body_launch(const PgBodyReduceArgs<double>& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_param_reduce_body<double>, dim3((unsigned)((a.B * a.P + 255) / 256)), dim3(256), 0, st, a);
-}

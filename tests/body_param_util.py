@@ -1,4 +1,4 @@
-"""The CPU-only yardstick of the body groups of the table gradient (link inertia, motors, limits), shared by tests/test_gpu_body_param_grad.py (the
+"""The CPU-only yardstick of the body groups of the table gradient (link inertia, motors, limits; the cases: tests/param_grad_util.py), shared by tests/test_gpu_body_param_grad.py (the
 kernels against the oracle's finite differences), tests/test_oracle_body_param_grad.py (the oracle's exact body adjoint against the same
 differences) and tests/test_gpu_body_param_grad_oracle.py (the kernels against that adjoint).  No GPU, no torch: the functions here run in spawned
 processes side by side."""
@@ -11,40 +11,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import tactilesimulation_amd.model.blob as Bl      # noqa: E402
-from tactilesimulation_amd.model.compiler import load_model      # noqa: E402
-from test_oracle_param_grad import case, loss_weights, oracle_episode      # noqa: E402
-
-BODY = ("inertial", "motor", "limit")
-ALL = ("contact",) + BODY
-KINDS = ("mass", "com", "inertia", "motor lo", "motor hi", "motor P", "motor D", "limit lo", "limit hi", "limit k")
-# (name, frames)
-MODELS = [("pusher", 4), ("tactile_insertion", 3), ("stable_grasp", 3), ("dclaw_position_control", 3), ("tactile_pad", 3), ("box_slide", 4),
-          ("pad_press", 4), ("slider_push", 4), ("ball_push", 4), ("bdf2:ball_push", 3), ("bdf2:tactile_pad", 3), ("small:3", 4), ("small:11", 4),
-          ("large:L3", 4), ("large:L7", 4), ("large:L16", 4), ("limit_push", 4)]
-# a second model whose lower AND upper limit springs act in every environment, without contact (so that fp32 keeps the oracle's branches): the
-# files that hold something to the oracle's exact adjoint run it beside MODELS
-LIMIT_CHAIN = ("limit_chain", 4)
-
-
-def kind_of(bc):
-    kind, _, f, _ = bc
-    return {"link": "mass" if f == "mass" else "com" if f.startswith("com") else "inertia"}.get(kind) or "%s %s" % (kind, f)
-
-
-def body_case(name, B, T):
-    """case() of tests/test_oracle_param_grad.py, and this file's own model: tests/models/limit_push.xml — a slider a force motor pushes below its
-    lower limit and an arm a position motor holds above its upper limit, both in the limit from the first sub-step on"""
-    if name == "limit_chain":      # tests/models/limit_chain.xml: the shoulder below its lower limit, the elbow above its upper one
-        m = load_model(os.path.join(HERE, "models", "limit_chain.xml"))
-        q0 = np.tile([[-0.25, 0.3]], (B, 1))
-        u = np.tile(np.array([[-0.6, 0.5], [-0.4, 0.45], [-0.7, 0.55], [-0.5, 0.4]])[None], (B, 1, 1))[:, :T]
-        return m, q0, np.zeros_like(q0), u, 2
-    if name != "limit_push":
-        return case(name, B, T)
-    m = load_model(os.path.join(HERE, "models", "limit_push.xml"))
-    q0 = np.tile([[-0.03, 0.25]], (B, 1))
-    u = np.tile(np.array([[-0.8, 0.6], [-0.6, 0.7], [-0.9, 0.5], [-0.7, 0.6]])[None], (B, 1, 1))[:, :T]
-    return m, q0, np.zeros_like(q0), u, 2
+from param_grad_util import ALL, BODY_KINDS as KINDS, body_case, kind_of, loss_weights, oracle_episode      # noqa: E402
 
 
 def _step(m, bc):

@@ -29,8 +29,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import tactilesimulation_amd.model.blob as Bl      # noqa: E402
 from tactilesimulation_amd.model.compiler import load_model      # noqa: E402
-from body_param_util import ALL, BODY, KINDS, MODELS, _differences, _step, body_case, kind_of      # noqa: E402,F401  (CPU-only: spawned processes import them)
-from test_oracle_param_grad import loss_weights      # noqa: E402
+from body_param_util import _differences, _step      # noqa: E402  (CPU-only: spawned processes import them)
+from param_grad_util import ALL, BODY, BODY_KINDS as KINDS, MODELS, body_case, gpu_episode, kind_of, loss_weights, make_sim as _sim, table_rows      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -98,48 +98,9 @@ def yardstick(name, T):
     return _YARD[key]
 
 
-def _sim(m, B, dtype, cap, lanes=0, static=False):
-    import random_corpus as RC
-    from tactilesimulation_amd.host.batch import BatchSim
-    sim = BatchSim(m, B, device=DEV, dtype=dtype, tape_capacity=cap)
-    sim.set_static(static)
-    if lanes:
-        RC.force_lanes(sim, m, lanes)
-    return sim
-
-
 def _episode(sim, tab, q0, qd0, u, S, w, groups=ALL, mode="episode", grad=True):
-    """forward of the episode and its adjoint: (table gradient or None, signatures, status, outputs, dL/du, carried adjoint)"""
-    B, T, dt = sim.B, u.shape[1], sim.dtype
-    sim.set_env_tables(tab)
-    sim.reset(torch.tensor(q0, device=DEV, dtype=dt), torch.tensor(qd0, device=DEV, dtype=dt), backward_flag=True)
-    ut = torch.tensor(np.ascontiguousarray(u.transpose(1, 0, 2)), device=DEV, dtype=dt)
-    out = sim.rollout(ut, S, want_qd=True)
-    sig = sim.branch_signature()
-    wq, wv, wt = (torch.tensor(x, device=DEV, dtype=dt).unsqueeze(1).expand(-1, B, -1).contiguous() for x in w)
-    g = None
-    if grad:
-        g = torch.zeros((B, sim.base_tables().shape[1]), device=DEV, dtype=dt)
-        sim.set_param_grad_groups(groups)
-        sim.set_param_grad(g)
-    nv, nt = sim.ndof_var, sim.ndof_tactile
-    if mode == "episode":
-        du = sim.backward_episode(T, S, wq, wv if nv else None, wt if nt else None)
-    elif mode == "halves":
-        h = T // 2
-        d1 = sim.backward_episode(T - h, S, wq[h:], wv[h:] if nv else None, wt[h:] if nt else None)
-        d0 = sim.backward_episode(h, S, wq[:h], wv[:h] if nv else None, wt[:h] if nt else None)
-        du = torch.cat([d0, d1], 0)
-    else:
-        du = []
-        for t in reversed(range(T)):
-            du.append(sim.backward_steps(S, wq[t], wv[t] if nv else None, wt[t] if nt else None))
-        du = torch.stack(du[::-1], 0)
-    sim.set_param_grad(None)
-    sim.set_param_grad_groups(("contact",))
-    lq, lv = sim.get_adjoint()
-    torch.cuda.synchronize()
-    return g, sig, out["status"], out, du, (lq, lv)
+    """gpu_episode with every group on unless told otherwise"""
+    return gpu_episode(sim, tab, q0, qd0, u, S, w, groups=groups, mode=mode, grad=grad)
 
 
 def _errors(Y, g):
@@ -398,6 +359,42 @@ def test_nothing_existing_changes(name, T, dtype):
     other = np.setdiff1d(np.arange(ga.shape[1]), pc + bc)
     assert torch.all(ga[:, other] == 0)
     assert sim.param_grad_groups() == ("contact",)
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["fp64", "fp32"])
+@pytest.mark.parametrize("B,lanes", [(5, 16), (3, 32)])
+def test_body_groups_alone_leave_the_contact_columns_at_the_sentinel(B, lanes, dtype):
+    """The contact group off and the body groups on, into a buffer whose body columns are 0 and whose other entries hold a sentinel: the body
+    columns equal those of an all-groups launch into the same buffer bit for bit, and every other entry — the contact columns too — still holds
+    the sentinel (the all-groups launch moves it there).  limit_push, 4 frames x 2 sub-steps, per-environment tables; B = 5 at 16 lanes (a ragged
+    last wavefront with an idle slot) and B = 3 at 32.  (test_nothing_existing_changes holds the same two properties at B = 4 into a zeroed buffer:
+    there an added zero or a stray store of 0 would not show, and no slot is idle.)"""
+    m, q0, qd0, u, S = body_case("limit_push", B, 4)
+    T = u.shape[1]
+    sim = _sim(m, B, dtype, T * S, lanes)
+    assert sim.launch_info()["lanes_per_env"] == lanes and B % (64 // lanes) != 0
+    sim.set_env_tables(torch.tensor(table_rows(m, B, dtype == torch.float32, 43), device=DEV, dtype=dtype))
+    ut = torch.tensor(np.ascontiguousarray(u.transpose(1, 0, 2)), device=DEV, dtype=dtype)
+    wq, wv, wt = (torch.tensor(x, device=DEV, dtype=dtype).unsqueeze(1).expand(-1, B, -1).contiguous() for x in loss_weights(m, T, 1))
+    pc = [c for (_, _, _, c) in m.param_columns()]
+    bc = [c for (_, _, _, c) in m.body_param_columns()]
+    got = {}
+    for groups in (BODY, ALL):
+        buf = torch.full((B, sim.base_tables().shape[1]), 7.0, device=DEV, dtype=dtype)
+        buf[:, bc] = 0.0
+        sim.reset(torch.tensor(q0, device=DEV, dtype=dtype), torch.tensor(qd0, device=DEV, dtype=dtype), backward_flag=True)
+        sim.rollout(ut, S)
+        sim.set_param_grad_groups(groups)
+        sim.set_param_grad(buf)
+        sim.backward_episode(T, S, wq, wv if sim.ndof_var else None, wt if sim.ndof_tactile else None)
+        sim.set_param_grad(None)
+        sim.set_param_grad_groups(("contact",))
+        torch.cuda.synchronize()
+        got[groups] = buf
+    other = np.setdiff1d(np.arange(got[ALL].shape[1]), bc)
+    assert torch.equal(got[BODY][:, bc], got[ALL][:, bc]) and got[ALL][:, bc].abs().max() > 0
+    assert torch.all(got[BODY][:, other] == 7.0)
+    assert torch.all(got[ALL][:, np.setdiff1d(other, pc)] == 7.0) and (got[ALL][:, pc] != 7.0).any()
 
 
 def test_groups_switch_refuses_unknown_bits_and_reads_back():

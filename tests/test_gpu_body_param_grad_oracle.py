@@ -1,4 +1,4 @@
-"""The body groups of the kernels' table gradient (tsim_set_param_grad_groups: k_backward_z -> k_param_grad_body -> k_param_reduce_body; link mass,
+"""The body groups of the kernels' table gradient (tsim_set_param_grad_groups: k_backward_z -> k_param_grad_body -> k_param_reduce; link mass,
 com, inertia; motor lo hi P D; limit lo hi k) against the fp64 CPU oracle's exact body adjoint (OracleSim.set_param_grad_groups, pinned to the
 oracle's own finite differences by tests/test_oracle_body_param_grad.py).
 
@@ -23,10 +23,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import tactilesimulation_amd.model.blob as Bl      # noqa: E402
-from body_param_util import ALL, KINDS, LIMIT_CHAIN, MODELS, body_case, kind_of      # noqa: E402
-from test_gpu_body_param_grad import _episode, _sim as _sim_lanes      # noqa: E402
-from test_gpu_param_grad_oracle import _layout_kind, _pg_layout, _pusher, _row_model      # noqa: E402
-from test_oracle_param_grad import oracle_episode      # noqa: E402
+from param_grad_util import (ALL, BODY_KINDS as KINDS, LIMIT_CHAIN, MODELS, body_case, gpu_episode, kind_of, layout_kind, loss_weights,      # noqa: E402
+                             make_sim as _sim, oracle_cached, pg_layout, pusher_case, row_model, table_rows)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -41,31 +39,6 @@ F32_99, F32_MAX = 1e-4, 1e-2
 ABOVE = 1e-3            # "above the floor" in the coverage counts: |g_oracle| >= 1e-3 S_kind
 LIMIT_KINDS = ("limit lo", "limit hi", "limit k")
 PUSHER_KINDS = ("mass", "com", "inertia", "motor lo", "motor hi")      # TactilePush: force motors, no limits
-_ORACLE = {}
-
-
-def _oracle(m, q0, qd0, u, S, w):
-    """(oracle gradient with every group on, signatures [n, 2], non-converged sub-steps) of one environment, cached across parametrisations"""
-    key = (m.F.tobytes(), m.I.tobytes(), q0.tobytes(), qd0.tobytes(), u.tobytes(), S, tuple(x.tobytes() for x in w))
-    if key not in _ORACLE:
-        L, g, sig, bad, _ = oracle_episode(m, q0, u, S, w, qd0=qd0, groups=ALL)
-        _ORACLE[key] = (g, sig, bad)
-    return _ORACLE[key]
-
-
-def _weights(m, T, seed=0):
-    rng = np.random.default_rng(seed)
-    return rng.normal(size=(T, m.ndof_r)), rng.normal(size=(T, m.ndof_var)), rng.normal(size=(T, m.ndof_tactile))
-
-
-def _rows(m, B, dtype, seed, lo=0.8, hi=1.25):
-    """[B, table_size] per-environment tables: every column a gradient is computed for — contact and body columns alike — scaled by a seeded
-    factor (numpy only, so that the cases can be examined without a GPU); rounded to the batch's type"""
-    n = int(m.I[Bl.TSIM_IH_FOFF_CPT])
-    cols = [c for (_, _, _, c) in m.param_columns() + m.body_param_columns()]
-    tab = np.tile(np.asarray(m.F[:n], dtype=np.float64), (B, 1))
-    tab[:, cols] *= np.random.default_rng(seed).uniform(lo, hi, size=(B, len(cols)))
-    return tab.astype(np.float32 if dtype == torch.float32 else np.float64)
 
 
 class Tally:
@@ -122,34 +95,25 @@ class Tally:
         return st
 
 
-def _sim(m, B, dtype, cap, lanes, static=False, tally=None):
-    """a batch at `lanes` lanes per environment; the shape the launch reports is read back (random_corpus.force_lanes asserts it: the forced one,
-    64 with a rotation-vector joint — the EXPJ instantiations exist at 64 lanes only —, wider only where the LDS does not fit) and recorded"""
-    sim = _sim_lanes(m, B, dtype, cap, lanes, static)
-    if tally is not None:
-        tally.lanes.add(sim.launch_info()["lanes_per_env"])
-    return sim
-
-
 def _compare_batch(tally, name, m, sim, rows, q0, qd0, u, S, w, envs, mode="episode", max_iter=None):
     """run the batch with every group on, then the oracle on the environments `envs` with their own rows; adds to tally"""
     if sim.dtype == torch.float32:                         # both sides start from the values the fp32 batch holds
         q0, qd0, u = (x.astype(np.float32).astype(np.float64) for x in (q0, qd0, u))
     tab = None if rows is None else torch.tensor(rows, device=DEV, dtype=sim.dtype)
-    g, sig, status, _, _, _ = _episode(sim, tab, q0, qd0, u, S, w, groups=ALL, mode=mode)
+    g, sig, status = gpu_episode(sim, tab, q0, qd0, u, S, w, groups=ALL, mode=mode)[:3]
     g, sig, status = g.double().cpu().numpy(), sig.cpu().numpy(), status.cpu().numpy()
     n = u.shape[1] * S
-    tally.layouts.add(_layout_kind(sim.B, n if mode == "episode" else S if mode == "steps" else (u.shape[1] - u.shape[1] // 2) * S))
+    tally.layouts.add(layout_kind(sim.B, n if mode == "episode" else S if mode == "steps" else (u.shape[1] - u.shape[1] // 2) * S))
     other = np.setdiff1d(np.arange(g.shape[1]), [c for (_, _, _, c) in m.param_columns() + m.body_param_columns()])
     assert np.all(g[:, other] == 0), name
     for e in envs:
         tally.envs += 1
-        om = m if rows is None else _row_model(m, rows[e].astype(np.float64))
+        om = m if rows is None else row_model(m, rows[e].astype(np.float64))
         if max_iter:
             om = copy.copy(om)
             om.I = om.I.copy()
             om.I[Bl.TSIM_IH_MAX_ITER] = max(int(om.I[Bl.TSIM_IH_MAX_ITER]), max_iter)
-        go, osig, obad = _oracle(om, q0[e], qd0[e], u[e], S, w)
+        go, osig, obad, _ = oracle_cached(om, q0[e], qd0[e], u[e], S, w, groups=ALL)[1]
         if obad or status[e] != 0 or not np.array_equal(sig[:, e], osig):
             continue
         tally.add(m, g[e], go, name, (name, int(e)))
@@ -184,7 +148,7 @@ def test_generic_body_gradient_against_the_oracle(lanes, dtype):
         info = sim.launch_info()
         assert info["lanes_per_env"] == (64 if RC.has_exp_joint(m) else lanes) or (info["lanes_per_env"] > lanes and info["lds_bytes"] <= 64 * 1024), (name, info)
         assert sim.kernel_variant() == "generic" or name == "pusher"
-        _compare_batch(tally, name, m, sim, _rows(m, B, dtype, 17), q0, qd0, u, S, _weights(m, u.shape[1]), range(B), max_iter=None if fp64 else 100)
+        _compare_batch(tally, name, m, sim, table_rows(m, B, not fp64, 17), q0, qd0, u, S, loss_weights(m, u.shape[1]), range(B), max_iter=None if fp64 else 100)
     assert exp_seen and lanes in tally.lanes, tally.lanes
     tally.check("generic_%s_lpe%d" % ("fp64" if fp64 else "fp32", lanes), KINDS, limit_models=True)
 
@@ -210,11 +174,11 @@ def test_ragged_batches(B, lanes, dtype):
     m = _tol(m, fp64)
     sim = _sim(m, B, dtype, u.shape[1] * S, lanes, tally=tally)
     assert sim.launch_info()["lanes_per_env"] == lanes and B % (64 // lanes) != 0
-    _compare_batch(tally, "limit_push", m, sim, _rows(m, B, dtype, 23), q0, qd0, u, S, _weights(m, u.shape[1]), range(B), max_iter=None if fp64 else 100)
+    _compare_batch(tally, "limit_push", m, sim, table_rows(m, B, not fp64, 23), q0, qd0, u, S, loss_weights(m, u.shape[1]), range(B), max_iter=None if fp64 else 100)
     m, q0, qd0, u, S = body_case("ball_push", B, 4)
     m = _tol(m, fp64)
     sim = _sim(m, B, dtype, u.shape[1] * S, lanes, tally=tally)
-    _compare_batch(tally, "ball_push", m, sim, _rows(m, B, dtype, 29), q0, qd0, u, S, _weights(m, u.shape[1]), range(B), max_iter=None if fp64 else 100)
+    _compare_batch(tally, "ball_push", m, sim, table_rows(m, B, not fp64, 29), q0, qd0, u, S, loss_weights(m, u.shape[1]), range(B), max_iter=None if fp64 else 100)
     tally.reached.add("ragged B=%d lanes=%d" % (B, lanes))
     tally.check("ragged_B%d_lpe%d_%s" % (B, lanes, "fp64" if fp64 else "fp32"), KINDS)
 
@@ -223,7 +187,7 @@ def test_ragged_batches(B, lanes, dtype):
 def _batch_for(kind, n):
     """the smallest batch (4, or a multiple of 256) whose body pass over n sub-steps has the chunk layout `kind` on this device"""
     for B in [4] + list(range(256, 65536 + 1, 256)):
-        if _layout_kind(B, n) == kind:
+        if layout_kind(B, n) == kind:
             return B
     raise AssertionError("no batch size gives the %s layout for %d sub-steps on this device" % (kind, n))
 
@@ -251,13 +215,13 @@ def test_chunk_layouts_of_the_body_pass(kind, dtype):
     kind, _, forced = kind.partition(":")
     B = int(forced) if forced else _batch_for(kind, T * 2)
     m, q0, qd0, u, S = _limit_push_case(B, T, 41)
-    assert S == 2 and _layout_kind(B, T * S) == kind
+    assert S == 2 and layout_kind(B, T * S) == kind
     m = _tol(m, fp64)
     sim = _sim(m, B, dtype, T * S, lanes, tally=tally)
     envs = _sample(B, 32, B, 64 // lanes) if B > 32 else range(B)
-    _compare_batch(tally, "limit_push", m, sim, _rows(m, B, dtype, 31), q0, qd0, u, S, _weights(m, T), envs, max_iter=None if fp64 else 100)
+    _compare_batch(tally, "limit_push", m, sim, table_rows(m, B, not fp64, 31), q0, qd0, u, S, loss_weights(m, T), envs, max_iter=None if fp64 else 100)
     assert tally.layouts == {kind}, tally.layouts
-    nchunk, cl = _pg_layout(B, T * S)
+    nchunk, cl = pg_layout(B, T * S)
     tally.reached.add("layout %s: B=%d nchunk=%d chunk_len=%d" % (kind, B, nchunk, cl))
     tally.check("layout_%s_B%d_%s" % (kind, B, "fp64" if fp64 else "fp32"), KINDS, share=fp64 or B >= 32)
 
@@ -267,15 +231,15 @@ def test_chunk_layouts_on_the_headline_shape(B):
     """the inertial case on the headline instantiation: fp32 param:pusher, 16 lanes, 10 frames x 5 sub-steps, per-environment tables — the shapes of
     the contact pass's layout test (B = 4096: 4 chunks of 13, the last one short; B = 16384: one chunk); 40 sampled environments go to the oracle"""
     T = 10
-    m, q0, qd0, u, S = _pusher(B, T, seed=11)
+    m, q0, qd0, u, S = pusher_case(B, T, seed=11)
     tally = Tally(False)
     sim = _sim(m, B, torch.float32, T * S, 16, static=True, tally=tally)
-    rows = _rows(m, B, torch.float32, 0)
+    rows = table_rows(m, B, True, 0)
     sim.set_env_tables(torch.tensor(rows, device=DEV))
     assert sim.kernel_variant() == "param:pusher"
     want = {4096: "ragged", 16384: "single"}[B]
-    assert _layout_kind(B, T * S) == want
-    _compare_batch(tally, "pusher", m, sim, rows, q0, qd0, u, S, _weights(m, T), _sample(B, 40, B, 4), max_iter=100)
+    assert layout_kind(B, T * S) == want
+    _compare_batch(tally, "pusher", m, sim, rows, q0, qd0, u, S, loss_weights(m, T), _sample(B, 40, B, 4), max_iter=100)
     assert sim.kernel_variant() == "param:pusher" and tally.layouts == {want} and tally.lanes == {16}
     tally.reached.add("headline B=%d %s" % (B, want))
     tally.check("headline_B%d" % B, PUSHER_KINDS)
@@ -295,7 +259,7 @@ def test_windows(mode, dtype):
         if name.startswith("bdf2:"):
             assert int(m.I[Bl.TSIM_IH_INTEGRATOR]) == 2 and (T - T // 2) * S >= 2 and (T // 2) * S >= 2
         sim = _sim(m, 4, dtype, u.shape[1] * S, 32, tally=tally)
-        _compare_batch(tally, name, m, sim, _rows(m, 4, dtype, 37), q0, qd0, u, S, _weights(m, u.shape[1]), range(4), mode=mode,
+        _compare_batch(tally, name, m, sim, table_rows(m, 4, not fp64, 37), q0, qd0, u, S, loss_weights(m, u.shape[1]), range(4), mode=mode,
                        max_iter=None if fp64 else 100)
     tally.reached.add("window %s" % mode)
     tally.check("window_%s_%s" % (mode, "fp64" if fp64 else "fp32"), KINDS)
@@ -309,7 +273,7 @@ def test_compiled_in_body_gradient_against_the_oracle(variant, dtype):
     fp64 = dtype == torch.float64
     tally = Tally(fp64)
     B, T = 8, 4
-    m, q0, qd0, u, S = _pusher(B, T)
+    m, q0, qd0, u, S = pusher_case(B, T)
     if variant == "param_edited":
         m = copy.deepcopy(m)
         m.F[m.I[Bl.TSIM_IH_FOFF_PAIR] + Bl.TSIM_PF_KN] *= 1.5
@@ -319,6 +283,6 @@ def test_compiled_in_body_gradient_against_the_oracle(variant, dtype):
     want = {"static": "static:pusher", "param_edited": "param:pusher"}[variant]
     sim = _sim(m, B, dtype, T * S, 32, static=True, tally=tally)
     assert sim.kernel_variant() == want, (sim.kernel_variant(), want)
-    _compare_batch(tally, "pusher", m, sim, None, q0, qd0, u, S, _weights(m, T), range(B), max_iter=None if fp64 else 100)
+    _compare_batch(tally, "pusher", m, sim, None, q0, qd0, u, S, loss_weights(m, T), range(B), max_iter=None if fp64 else 100)
     assert sim.kernel_variant() == want
     tally.check("%s_%s" % (variant, "fp64" if fp64 else "fp32"), PUSHER_KINDS)

@@ -20,8 +20,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import tactilesimulation_amd.model.blob as Bl      # noqa: E402
-from tactilesimulation_amd.model.compiler import load_model, parse_xml, compile_spec      # noqa: E402
+from tactilesimulation_amd.model.compiler import load_model      # noqa: E402
 from tactilesimulation_amd.workloads import asset, push_workload      # noqa: E402
+from param_grad_util import bdf2_case, fixed_case as _case, gpu_episode      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -37,87 +38,21 @@ def _sim(m, B, dtype=torch.float64, cap=64, static=False, lanes=0):
     return sim
 
 
-def _case(name, B):
-    """model, q0 [B, nr], u [B, T, nu], sub-steps per frame: a few frames in contact"""
-    from test_gpu_models import CASES, _inputs
-    if name.startswith("random"):
-        from test_native_model_loader import _random_model
-        rng = np.random.default_rng(5000 + int(name[6:]))
-        import tempfile
-        d = tempfile.mkdtemp(prefix="tsim_pg_")
-        for _ in range(20):
-            p = os.path.join(d, "m.xml")
-            open(p, "w").write(_random_model(rng, max_dof=10))
-            spec = parse_xml(p)
-            m = compile_spec(spec)
-            if 1 <= m.ndof_r <= 16 and m.ndof_u <= 16 and sum(J["type"] == "free3d-exp" for J in spec["joints"]) <= 1:
-                break
-        else:
-            pytest.skip("no model within the kernels' sizes")
-        q0 = np.tile(0.02 * rng.normal(size=(1, m.ndof_r)), (B, 1))
-        u = np.tile(rng.uniform(-1, 1, size=(1, 4, max(m.ndof_u, 1)))[:, :, :m.ndof_u], (B, 1, 1))
-        return m, q0, u, 2
-    if name.startswith("large:"):      # the large corpus of tests/random_corpus.py (ndof_r 13 .. 16)
-        import pathlib
-        import tempfile
-        import random_corpus as RC
-        m, rng = RC.draw(name[6:], pathlib.Path(tempfile.mkdtemp(prefix="tsim_pg_")))
-        q0 = np.tile(0.02 * rng.normal(size=(1, m.ndof_r)), (B, 1))
-        u = np.tile(rng.uniform(-1, 1, size=(1, 4, max(m.ndof_u, 1)))[:, :, :m.ndof_u], (B, 1, 1))
-        return m, q0, u, 2
-    p = os.path.join(HERE, "models", name + ".xml")
-    m = load_model(p if os.path.exists(p) else asset(name))
-    if name == "pusher":
-        q0, u, _ = push_workload(B, 12, seed=3)
-        u[:, :, 0] = 0.9                                                 # drive the pad into the box
-        return m, q0, u, 5
-    if name == "stable_grasp":
-        q0 = np.zeros((B, m.ndof_r)); u = np.zeros((B, 6, m.ndof_u)); u[:, :, -2:] = 1.0
-        return m, q0, u, 1
-    if name == "tactile_pad":
-        q0 = np.zeros((B, m.ndof_r)); u = np.zeros((B, 70, 3)); u[:, :, 2] = 0.2; u[:, 60:, 0] = 0.1
-        return m, q0, u, 2
-    T, S = CASES[name][2], CASES[name][3]
-    q0, u = _inputs(name, m, B, T)
-    return m, q0, u, S
-
-
 def _loss_weights(m, T, nm, seed=0):
     rng = np.random.default_rng(seed)
     return (rng.normal(size=(T, m.ndof_r)), rng.normal(size=(T, m.ndof_var)), rng.normal(size=(nm, m.ndof_tactile)))
 
 
-def _run(sim, tab, q0, u, S, w, grad=True, episode=True, pre=None):
+def _run(sim, tab, q0, u, S, w, grad=True, episode=True):
     """forward of the episode + its adjoint with the table gradient: (loss per env, table gradient, signatures, status, outputs, df_du, adjoint)"""
-    B, T = sim.B, u.shape[1]
-    dt = sim.dtype
-    if tab is not None:
-        sim.set_env_tables(tab)
-    sim.reset(torch.tensor(q0, device=DEV, dtype=dt), None, backward_flag=True)
-    ut = torch.tensor(np.ascontiguousarray(u.transpose(1, 0, 2)), device=DEV, dtype=dt)
-    out = sim.rollout(ut, S, want_qd=True)
-    wq, wv, wt = (torch.tensor(x, device=DEV, dtype=dt).unsqueeze(1).expand(-1, B, -1).contiguous() for x in w)
+    g, sig, status, out, du, adj = gpu_episode(sim, tab, q0, None, u, S, w, mode="episode" if episode else "steps", grad=grad)
+    wq, wv, wt = (torch.tensor(x, device=DEV, dtype=sim.dtype).unsqueeze(1) for x in w)
     L = (out["q"].double() * wq.double()).sum((0, 2))
     if sim.ndof_var:
         L = L + (out["var"].double() * wv.double()).sum((0, 2))
     if sim.ndof_tactile:
         L = L + (out["tactile"].double() * wt.double()).sum((0, 2))
-    sig = sim.branch_signature()
-    g = None
-    if grad:
-        g = torch.full((B, sim.base_tables().shape[1]), 0.0, device=DEV, dtype=dt) if pre is None else pre
-        sim.set_param_grad(g)
-    if episode:
-        du = sim.backward_episode(T, S, wq, wv if sim.ndof_var else None, wt if sim.ndof_tactile else None)
-    else:
-        du = []
-        for t in reversed(range(T)):
-            du.append(sim.backward_steps(S, wq[t], wv[t] if sim.ndof_var else None, wt[t] if sim.ndof_tactile else None))
-        du = torch.stack(du[::-1], 0)
-    sim.set_param_grad(None)
-    lq, lv = sim.get_adjoint()
-    torch.cuda.synchronize()
-    return L, g, sig, out["status"], out, du, (lq, lv)
+    return L, g, sig, status, out, du, adj
 
 
 FD_MODELS = ["pusher", "tactile_insertion", "stable_grasp", "dclaw_position_control", "tactile_pad", "box_slide", "pad_press", "sphere_rest",
@@ -264,7 +199,6 @@ def test_nothing_existing_changes_with_the_gradient_on(variant, dtype, lanes, ep
 
 @pytest.mark.parametrize("name", ["tactile_pad", "ball_push"])
 def test_nothing_existing_changes_on_bdf2(name):
-    from test_gpu_bdf2_adjoint import _case as bdf2_case
     m, q0, u, S = bdf2_case(name)
     for dtype in (torch.float64, torch.float32):
         sim = _sim(m, q0.shape[0], dtype=dtype, cap=u.shape[1] * S)
@@ -275,7 +209,6 @@ def test_nothing_existing_changes_on_bdf2(name):
 
 
 def test_bdf2_gradient_equals_finite_differences():
-    from test_gpu_bdf2_adjoint import _case as bdf2_case
     m, q0, u, S = bdf2_case("ball_push")
     errs, total = _fd_compare(m, q0, u[:, :6], S, nbase=1)
     assert errs.size > 0 and np.mean(errs <= 1e-6) >= 0.99 and errs.max() <= 1e-3, errs

@@ -21,9 +21,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import tactilesimulation_amd.model.blob as Bl      # noqa: E402
-from tactilesimulation_amd.model.compiler import load_model      # noqa: E402
-from tactilesimulation_amd.workloads import asset, push_workload      # noqa: E402
-from test_oracle_param_grad import case, kind_of, KINDS, oracle_episode      # noqa: E402
+from param_grad_util import CONTACT_KINDS as KINDS, case, gpu_episode, kind_of, layout_kind, loss_weights, make_sim, oracle_cached, pusher_case, row_model      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -44,36 +42,7 @@ FD_FIXED = ["pusher", "tactile_insertion", "stable_grasp", "dclaw_position_contr
 GENERIC_MODELS = FD_FIXED + ["random%d" % k for k in range(20)] + ["large:L26", "large:L7", "large:L16", "large:L3", "large:L10", "large:L0", "small:5", "bdf2:tactile_pad",
                              "bdf2:ball_push"]
 FRAMES = {"tactile_pad": 3, "bdf2:tactile_pad": 3, "dclaw_position_control": 3, "tactile_insertion": 3, "stable_grasp": 4}
-_ORACLE = {}
-
-
-def _pg_layout(B, n):
-    """(nchunk, chunk_len) of k_param_grad for a launch of n sub-steps (tsim_hip.hip pg_chunks_for)"""
-    n_simd = 4 * torch.cuda.get_device_properties(0).multi_processor_count
-    want = max(1, (16 * n_simd + B - 1) // B)
-    nchunk = max(1, min(n, want))
-    cl = (n + nchunk - 1) // nchunk
-    return (n + cl - 1) // cl, cl
-
-
-def _layout_kind(B, n):
-    nchunk, cl = _pg_layout(B, n)
-    return "single" if nchunk == 1 else "len1" if cl == 1 else "ragged" if n % cl else "even"
-
-
-def _oracle(key, m, q0, qd0, u, S, w, tac_mask=None):
-    """(oracle gradient, signatures [n, 2], non-converged, frame states) of one environment, cached across parametrisations"""
-    if key not in _ORACLE:
-        L, g, sig, bad, states = oracle_episode(m, q0, u, S, w, tac_mask=tac_mask, qd0=qd0)
-        _ORACLE[key] = (g, sig, bad, states)
-    return _ORACLE[key]
-
-
-def _row_model(m, row):
-    me = copy.copy(m)
-    me.F = m.F.copy()
-    me.F[:row.size] = row
-    return me
+_FLAGS = {}
 
 
 class Tally:
@@ -152,85 +121,37 @@ def _states_flags(o_states, m, om, keep):
     return slip, tslip, tmove, tail
 
 
-def _gpu_episode(sim, tab, q0, qd0, u, S, w, mode="episode", tac_mask=None):
-    """forward of the episode + its adjoint with the table gradient: (gradient [B, n], signatures [n_sub, B, 2], status [B])"""
-    B, T, dt = sim.B, u.shape[1], sim.dtype
-    if tab is not None:
-        sim.set_env_tables(tab)
-    sim.reset(torch.tensor(q0, device=DEV, dtype=dt), torch.tensor(qd0, device=DEV, dtype=dt), backward_flag=True)
-    ut = torch.tensor(np.ascontiguousarray(u.transpose(1, 0, 2)), device=DEV, dtype=dt)
-    mask = None if tac_mask is None else torch.tensor(tac_mask, dtype=torch.bool)
-    out = sim.rollout(ut, S, tactile_mask=mask)
-    sig = sim.branch_signature()
-    wq, wv, wt = (torch.tensor(x, device=DEV, dtype=dt).unsqueeze(1).expand(-1, B, -1).contiguous() for x in w)
-    if mask is not None:
-        wt = wt[mask.to(DEV)].contiguous()
-    g = torch.zeros((B, sim.base_tables().shape[1]), device=DEV, dtype=dt)
-    sim.set_param_grad(g)
-    nv, nt = sim.ndof_var, sim.ndof_tactile
-    if mode == "episode":
-        sim.backward_episode(T, S, wq, wv if nv else None, wt if nt else None, tactile_mask=mask)
-    elif mode == "halves":
-        h = T // 2
-        sim.backward_episode(T - h, S, wq[h:], wv[h:] if nv else None, wt[h:] if nt else None)
-        sim.backward_episode(h, S, wq[:h], wv[:h] if nv else None, wt[:h] if nt else None)
-    else:
-        for t in reversed(range(T)):
-            sim.backward_steps(S, wq[t], wv[t] if nv else None, wt[t] if nt else None)
-    sim.set_param_grad(None)
-    torch.cuda.synchronize()
-    return g.double().cpu().numpy(), sig.cpu().numpy(), out["status"].cpu().numpy()
-
-
 def _compare_batch(tally, key, m, sim, tab, q0, qd0, u, S, w, envs, mode="episode", tac_mask=None, max_iter=None):
     """Run the batch, then the oracle on the environments `envs`; adds to tally"""
-    g, sig, status = _gpu_episode(sim, tab, q0, qd0, u, S, w, mode, tac_mask)
+    g, sig, status = gpu_episode(sim, tab, q0, qd0, u, S, w, mode=mode, tac_mask=tac_mask, want_qd=False)[:3]
+    g, sig, status = g.double().cpu().numpy(), sig.cpu().numpy(), status.cpu().numpy()
     n = u.shape[1] * S
-    tally.layouts.add(_layout_kind(sim.B, n if mode != "steps" else S))
+    tally.layouts.add(layout_kind(sim.B, n if mode != "steps" else S))
     rows = (tab if tab is not None else sim.base_tables()).double().cpu().numpy()
     pcols = m.param_columns()
     other = np.setdiff1d(np.arange(g.shape[1]), [c for (_, _, _, c) in pcols])
     assert np.all(g[:, other] == 0), key
-    tol = float(rows[0, Bl.TSIM_FH_TOL])
     for e in envs:
         tally.envs += 1
-        om = _row_model(m, rows[e])
+        om = row_model(m, rows[e])
         if max_iter:
             om.I = om.I.copy()
             om.I[Bl.TSIM_IH_MAX_ITER] = max(int(om.I[Bl.TSIM_IH_MAX_ITER]), max_iter)
-        rk = (key, tol, max_iter, rows[e].tobytes(), q0[e].tobytes(), qd0[e].tobytes(), u[e].tobytes(), None if tac_mask is None else tuple(tac_mask))
-        go, osig, obad, ost = _oracle(rk, om, q0[e], qd0[e], u[e], S, w, tac_mask)
+        rk, (go, osig, obad, ost) = oracle_cached(om, q0[e], qd0[e], u[e], S, w, tac_mask)
         if obad or status[e] != 0 or not np.array_equal(sig[:, e], osig):
             continue
-        fk = ("flags",) + rk
-        if fk not in _ORACLE:
-            _ORACLE[fk] = _states_flags(ost, m, om, np.ones(u.shape[1], bool) if tac_mask is None else tac_mask)
-        tally.add(m, g[e], go, pcols, *_ORACLE[fk], tag=(key, e))
-
-
-def _weights(m, T, seed=0):
-    rng = np.random.default_rng(seed)
-    return rng.normal(size=(T, m.ndof_r)), rng.normal(size=(T, m.ndof_var)), rng.normal(size=(T, m.ndof_tactile))
+        if rk not in _FLAGS:
+            _FLAGS[rk] = _states_flags(ost, m, om, np.ones(u.shape[1], bool) if tac_mask is None else tac_mask)
+        tally.add(m, g[e], go, pcols, *_FLAGS[rk], tag=(key, e))
 
 
 def _tables(sim, m, seed, lo=0.8, hi=1.25):
+    """per-environment tables: the contact columns of the batch's own (rounded) tables scaled by a seeded factor — another draw than
+    param_grad_util.table_rows, which scales the body columns too"""
     cols = [c for (_, _, _, c) in m.param_columns()]
     tab = sim.base_tables().double()
     tab[:, cols] *= torch.tensor(np.random.default_rng(seed).uniform(lo, hi, size=(sim.B, len(cols))), device=DEV)
     return tab.to(sim.dtype)
-
-
-def _sim(m, B, dtype, cap, lanes, static=False, tally=None):
-    """a batch at `lanes` lanes per environment (the explicit setting wins over TSIM_LPE); the shape the launch reports is checked
-    (random_corpus.force_lanes: wider only for a rotation-vector joint or where the LDS does not fit) and recorded"""
-    import random_corpus as RC
-    from tactilesimulation_amd.host.batch import BatchSim
-    sim = BatchSim(m, B, device=DEV, dtype=dtype, tape_capacity=cap)
-    sim.set_static(static)
-    got = RC.force_lanes(sim, m, lanes)
-    if tally is not None:
-        tally.lanes.add(got)
-    return sim
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["fp64", "fp32"])
@@ -248,10 +169,10 @@ def test_generic_table_gradient_against_the_oracle(lanes, dtype):
         if fp64:
             m.F[Bl.TSIM_FH_TOL] = 1e-13
         exp_seen |= RC.has_exp_joint(m)
-        sim = _sim(m, B, dtype, u.shape[1] * S, lanes, tally=tally)
+        sim = make_sim(m, B, dtype, u.shape[1] * S, lanes, tally=tally)
         tab = _tables(sim, m, 17)
         assert sim.kernel_variant() == "generic" or name == "pusher"
-        _compare_batch(tally, ("generic", name), m, sim, tab, q0, qd0, u, S, _weights(m, u.shape[1]), range(B),
+        _compare_batch(tally, ("generic", name), m, sim, tab, q0, qd0, u, S, loss_weights(m, u.shape[1]), range(B),
                        max_iter=None if fp64 else 100)
     assert exp_seen and lanes in tally.lanes, tally.lanes
     tally.check("generic_%s_lpe%d" % ("fp64" if fp64 else "fp32", lanes))
@@ -262,13 +183,6 @@ PUSHER_GROUPS = [("static", torch.float32, 16), ("static", torch.float32, 32), (
                  ("param_edited", torch.float64, 32), ("param_edited", torch.float64, 64)]
 
 
-def _pusher(B, T, seed=3):
-    m = load_model(asset("pusher"))
-    q0, u, _ = push_workload(B, T + 2, seed=seed)
-    u[:, :, 0] = 0.9                                                   # the pad dragged into and across the box
-    return m, q0, np.zeros_like(q0), u[:, 2:], 5
-
-
 @pytest.mark.parametrize("variant,dtype,lanes", PUSHER_GROUPS)
 def test_compiled_in_table_gradient_against_the_oracle(variant, dtype, lanes):
     """static:pusher / param:pusher (the fused k_backward_z with taped K feeds k_param_grad): episode and step windows, a tactile mask with
@@ -276,7 +190,7 @@ def test_compiled_in_table_gradient_against_the_oracle(variant, dtype, lanes):
     fp64 = dtype == torch.float64
     tally = Tally(fp64)
     T = 6
-    m, q0, qd0, u, S = _pusher(13, T)
+    m, q0, qd0, u, S = pusher_case(13, T)
     if variant == "param_edited":
         m = copy.deepcopy(m)
         m.F[m.I[Bl.TSIM_IH_FOFF_PAIR] + Bl.TSIM_PF_KN] *= 1.5
@@ -285,10 +199,10 @@ def test_compiled_in_table_gradient_against_the_oracle(variant, dtype, lanes):
         m = copy.deepcopy(m)                                            # the fp64 kernels run the oracle's Newton loop at any tol)
         m.F[Bl.TSIM_FH_TOL] = 1e-13
     want = {"static": "static:pusher", "param": "param:pusher", "param_edited": "param:pusher"}[variant]
-    w = _weights(m, T)
+    w = loss_weights(m, T)
     mask = [True, False, True, True, False, True]
     for mode, tm in (("episode", None), ("steps", None), ("halves", None), ("episode", mask)):
-        sim = _sim(m, 13, dtype, T * S, lanes, static=True, tally=tally)
+        sim = make_sim(m, 13, dtype, T * S, lanes, static=True, tally=tally)
         tab = _tables(sim, m, 5) if variant == "param" else None
         if tab is not None:
             sim.set_env_tables(tab)
@@ -304,15 +218,15 @@ def test_chunk_layouts_on_the_headline_shape(B):
     """fp32 param:pusher, 16 lanes, 10 frames x 5 sub-steps, randomised kn / kt / mu / kd / damping tables: B = 4096 runs chunk_len > 1 with a
     shorter last chunk, B = 16384 a single chunk; a seeded sample of 48 environments goes to the oracle"""
     T = 10
-    m, q0, qd0, u, S = _pusher(B, T, seed=11)
+    m, q0, qd0, u, S = pusher_case(B, T, seed=11)
     tally = Tally(False)
-    sim = _sim(m, B, torch.float32, T * S, 16, static=True, tally=tally)
+    sim = make_sim(m, B, torch.float32, T * S, 16, static=True, tally=tally)
     tab = _tables(sim, m, 0)
     sim.set_env_tables(tab)
     assert sim.kernel_variant() == "param:pusher"
     want = {4096: "ragged", 16384: "single"}[B]
-    assert _layout_kind(B, T * S) == want
+    assert layout_kind(B, T * S) == want
     envs = np.sort(np.random.default_rng(B).choice(B, 48, replace=False))
-    _compare_batch(tally, ("headline", B), m, sim, tab, q0, qd0, u, S, _weights(m, T), envs, max_iter=100)
+    _compare_batch(tally, ("headline", B), m, sim, tab, q0, qd0, u, S, loss_weights(m, T), envs, max_iter=100)
     assert tally.layouts == {want}
     tally.check("headline_B%d" % B, kinds=F32_PUSHER_KINDS, need_tail=True)

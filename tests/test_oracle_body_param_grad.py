@@ -19,8 +19,8 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import tactilesimulation_amd.model.blob as Bl      # noqa: E402
-from body_param_util import ALL, BODY, KINDS, LIMIT_CHAIN, MODELS, _step, body_case, kind_of, oracle_body_check      # noqa: E402
-from test_oracle_param_grad import loss_weights, oracle_episode      # noqa: E402
+from body_param_util import _step, oracle_body_check      # noqa: E402
+from param_grad_util import ALL, BODY, BODY_KINDS as KINDS, LIMIT_CHAIN, MODELS, body_case, kind_of, loss_weights, oracle_episode      # noqa: E402
 
 TOL = 1e-15
 CASES = MODELS + [LIMIT_CHAIN]      # the yardstick's 17 models and the second limit model of the GPU file

@@ -8,11 +8,8 @@ parameter column, Richardson-extrapolated ((4 D(h/2) - D(h)) / 3), at Newton tol
 column is held relative to its own finite-difference value, with a floor of a small fraction of the largest entry of the gradient (the
 finite-difference noise is far below it).  Entries outside model.param_columns() stay exactly 0."""
 import copy
-import functools
 import os
-import pathlib
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -20,8 +17,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import tactilesimulation_amd.model.blob as Bl      # noqa: E402
-from tactilesimulation_amd.model.compiler import load_model      # noqa: E402
-from tactilesimulation_amd.workloads import asset, push_workload      # noqa: E402
+from param_grad_util import CONTACT_KINDS as KINDS, case, kind_of, loss_weights, oracle_episode      # noqa: E402
 
 FD_FIXED = ["pusher", "tactile_insertion", "stable_grasp", "dclaw_position_control", "tactile_pad", "box_slide", "pad_press", "sphere_rest",
             "slider_push", "ball_push"]
@@ -29,97 +25,6 @@ BDF2 = ["bdf2:tactile_pad", "bdf2:ball_push"]
 RANDOM = ["small:%d" % k for k in (1, 3, 5, 8, 11, 14, 17, 21, 26, 31, 37, 44)] + ["large:L26", "large:L7", "large:L16", "large:L3", "large:L10",
                                                                                    "large:L45", "large:L0", "large:L2"]
 FLOOR = 1e-5        # of the row's largest entry: the finite differences' own noise is about 2e-8 of it (measured: profiles/r10_param_grad_oracle.md)
-KINDS = ("pair kn", "pair kt", "pair mu", "pair damping", "sensor kn", "sensor kt", "sensor mu", "sensor damping", "dof damping")
-
-
-@functools.lru_cache(maxsize=None)
-def _preroll(name, S):
-    """(q, qd) of the tactile_pad case after its first 56 frames (pressed on the ball, just before the drag), on the oracle"""
-    from oracle.oracle import OracleSim
-    from test_gpu_bdf2_adjoint import _case as bdf2_case
-    from test_gpu_param_grad import _case as pg_case
-    m, q0, u, S = bdf2_case(name[5:]) if name.startswith("bdf2:") else pg_case(name, 1)
-    o = OracleSim(m)
-    o.reset(q0[0])
-    for t in range(56):
-        o.forward(u[0, t], S)
-    return o.state()
-
-
-def case(name, B, T=None):
-    """model, q0 [B, nr], qd0 [B, nr], u [B, T, nu], sub-steps per frame.  The same inputs as the kernels' tests
-    (tests/test_gpu_param_grad.py _case, tests/test_gpu_bdf2_adjoint.py _case, tests/random_corpus.py)."""
-    if name.startswith("bdf2:"):
-        from test_gpu_bdf2_adjoint import _case as bdf2_case
-        m, q0, u, S = bdf2_case(name[5:])
-        q0, u = np.resize(q0, (B, q0.shape[1])), np.resize(u, (B,) + u.shape[1:])
-    elif name.startswith(("small:", "large:")):
-        import random_corpus as RC
-        cid = int(name[6:]) if name.startswith("small:") else name[6:]
-        got = RC.draw(cid, pathlib.Path(tempfile.mkdtemp(prefix="tsim_opg_")))
-        if got is None:
-            raise AssertionError("no model within the kernels' sizes for %s" % name)
-        m, rng = got
-        q0 = np.tile(0.02 * rng.normal(size=(1, m.ndof_r)), (B, 1))
-        u = np.tile(rng.uniform(-1, 1, size=(1, 4, max(m.ndof_u, 1)))[:, :, :m.ndof_u], (B, 1, 1))
-        S = 2
-    else:
-        from test_gpu_param_grad import _case as pg_case
-        m, q0, u, S = pg_case(name, B)
-    qd0 = np.zeros_like(q0)
-    if name.endswith("tactile_pad"):                                     # start pressed on the ball, just before the drag (frame 56 of the case)
-        q, qd = _preroll(name, S)
-        q0, qd0, u = np.tile(q, (B, 1)), np.tile(qd, (B, 1)), u[:, 56:]
-    if T is not None:
-        u = u[:, :T]
-    return m, q0, qd0, u, S
-
-
-def loss_weights(m, T, seed=0):
-    rng = np.random.default_rng(seed)
-    return rng.normal(size=(T, m.ndof_r)), rng.normal(size=(T, m.ndof_var)), rng.normal(size=(T, m.ndof_tactile))
-
-
-def kind_of(pc):
-    """'pair kn' ... 'dof damping' of a param_columns() entry"""
-    return "%s %s" % (pc[0], pc[2])
-
-
-def oracle_episode(m, q0, u, S, w, grad=True, tac_mask=None, qd0=None, groups=None):
-    """One environment on the fp64 oracle from (q0, qd0): the frames of u [T, nu], the loss sum_t wq[t].q_t + wv[t].var_t + wt[k].tac_t at each frame's end
-    (tac only at the frames tac_mask keeps, seeded by their own rows of wt), and its adjoint frame by frame with the table gradient on.
-    groups: OracleSim.set_param_grad_groups' names (None: the default, the contact columns).
-    Returns (loss, table gradient [table_size] or None, signatures [T S, 2], non-converged sub-steps, frame states [(q, qd)])."""
-    from oracle.oracle import OracleSim
-    o = OracleSim(m)
-    nr, T = m.ndof_r, u.shape[0]
-    wq, wv, wt = w
-    keep = np.ones(T, bool) if tac_mask is None else np.asarray(tac_mask, bool)
-    o.reset(q0, qd0, record=grad)
-    L, sigs, bad, states = 0.0, [], 0, []
-    for t in range(T):
-        b, sg = o.forward_sig(u[t], S)
-        bad += b
-        sigs.append(sg)
-        q, qd = o.state()
-        var, tac = o.outputs(tactile=bool(m.ndof_tactile) and keep[t])
-        states.append((q, qd))
-        L += float(wq[t] @ q) + (float(wv[t] @ var) if m.ndof_var else 0.0) + (float(wt[t] @ tac) if m.ndof_tactile and keep[t] else 0.0)
-    g = None
-    if grad:
-        g = np.zeros(o._L.orc_table_size(o._h))
-        o.set_param_grad(g)
-        if groups is not None:
-            o.set_param_grad_groups(groups)
-        for t in reversed(range(T)):
-            dq = np.zeros((S, nr)); dq[-1] = wq[t]
-            dv = np.zeros((S, m.ndof_var)); dv[-1] = wv[t]
-            dt = np.zeros((S, m.ndof_tactile))
-            if keep[t]:
-                dt[-1] = wt[t]
-            o.backward_steps(S, dq, dv if m.ndof_var else None, dt if m.ndof_tactile else None)
-        o.set_param_grad(None)
-    return L, g, np.concatenate(sigs, 0), bad, states
 
 
 def fd_compare(m, q0, qd0, u, S, hrel=1e-4, floor=FLOOR, seed=1, max_cols=10):

@@ -1,6 +1,7 @@
 """Cost of the parameter gradient (include/tsim.h tsim_set_param_grad): backward_episode of an open-loop episode with and without the table
 gradient, device events, median of 5 windows.  Default: TactilePush at B = 4096 fp32 (param:pusher with per-environment tables), 20 frames x 5
-sub-steps; --model stable_grasp / tactile_insertion for the other two.  One JSON line per configuration (profiles/r07_param_grad.md)."""
+sub-steps; --model stable_grasp / tactile_insertion for the other two; --groups contact,inertial,motor,limit (or all) for the body groups' pass as
+well (BatchSim.set_param_grad_groups; default: contact).  One JSON line per configuration (profiles/r07_param_grad.md)."""
 import argparse
 import json
 import os
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--groups", default="contact", help="comma-separated groups of the table gradient, or 'all'")
     a = ap.parse_args()
     m = load_model(asset(a.model))
     q0, u, S = inputs(a.model, m, a.B, a.frames)
@@ -40,13 +42,15 @@ def main():
     sim = BatchSim(m, a.B, dtype=torch.float32, tape_capacity=T * S)
     tab = sim.base_tables()
     sim.set_env_tables(tab)
+    groups = tuple(BatchSim.PARAM_GRAD_GROUPS) if a.groups == "all" else tuple(a.groups.split(","))
+    sim.set_param_grad_groups(groups)
     dev = sim.device
     q0t = torch.tensor(q0, device=dev, dtype=torch.float32)
     ut = torch.tensor(np.ascontiguousarray(u.transpose(1, 0, 2)), device=dev, dtype=torch.float32)
     g = torch.zeros_like(tab)
     wq = torch.randn(T, a.B, m.ndof_r, device=dev)
     wt = torch.randn(T, a.B, m.ndof_tactile, device=dev) if m.ndof_tactile else None
-    res = {"model": a.model, "B": a.B, "frames": T, "substeps": S, "variant": sim.kernel_variant()}
+    res = {"model": a.model, "B": a.B, "frames": T, "substeps": S, "variant": sim.kernel_variant(), "groups": list(groups)}
     for on in (False, True, False, True):
         times = []
         for _ in range(a.windows):

@@ -251,9 +251,14 @@ const char* tsim_kernel_variant(const tsim_batch* b);
 /* Read-only through tsim_get_option (set them with tsim_set_solver_options): TSIM_OPT_CROSS_KINKS, TSIM_OPT_EVAL_BUDGET; and TSIM_OPT_ALL_DEFAULT = 1 iff
  * every solver / scheduling option of the batch is at its default (cross_kinks 1, eval_budget 0, value_trials 2, trial_helpers 1, value_first 1) — the
  * forward launch of an fp32 batch on a compiled-in model at four environments per wavefront then runs an instantiation that has them as compile-time
- * constants (same results bit for bit, ~2 % faster; environment variable TSIM_NO_DEFAULT_OPTS=1 at creation: never). */
+ * constants (same results bit for bit, ~2 % faster; environment variable TSIM_NO_DEFAULT_OPTS=1 at creation: never).
+ * TSIM_OPT_FRAME_RECORDS (read-only): how the newest forward launch wrote its frames' q / qd / variables / pose records.  0: inside the forward kernel, at
+ * the end of each frame; 1: after it, from the tape, by the frame-record pass — tsim_rollout launches of more than one frame on a fused compiled-in
+ * model that record a tape and read the tactile frames out after the launch; 2: ... and the forward kernel was the instantiation that has this as a
+ * compile-time constant (every option at its default).  The same results bit for bit (tests/test_gpu_frame_records.py); environment variable
+ * TSIM_INKERNEL_FRAME_OUT=1 at creation: always 0. */
 enum { TSIM_OPT_PAIR_CULL = 1, TSIM_OPT_VALUE_TRIALS = 2, TSIM_OPT_TRIAL_HELPERS = 3, TSIM_OPT_VALUE_FIRST = 4, TSIM_OPT_CROSS_KINKS = 5, TSIM_OPT_EVAL_BUDGET = 6,
-       TSIM_OPT_ALL_DEFAULT = 7 };
+       TSIM_OPT_ALL_DEFAULT = 7, TSIM_OPT_FRAME_RECORDS = 8 };
 int tsim_set_option(tsim_batch* b, int option, int value);
 int tsim_get_option(const tsim_batch* b, int option);
 

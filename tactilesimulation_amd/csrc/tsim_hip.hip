@@ -436,12 +436,13 @@ struct tsim_batch {
   int nsched;                    // ints of the sweep schedule appended to dI
   int stage_cpt;                 // the contact-point arrays are staged in LDS with the shared tables
   int n_simd;                    // SIMDs of the device (CUs x 4)
+  int last_frame_rec = 0;        // the newest forward launch left its frames' outputs to k_frame_records (1; 2: and ran k_forward_fr; tsim_get_option TSIM_OPT_FRAME_RECORDS)
   int value_trials = 2;          // line-search trials after this many rejected ones evaluate the residual only (0: off; tsim_set_option TSIM_OPT_VALUE_TRIALS; TSIM_VALUE_TRIALS=n at creation)
   int trial_helpers = 1;        // finished slots of a wavefront evaluate the next line-search trials of a slot that is still in one (tsim_set_option TSIM_OPT_TRIAL_HELPERS; TSIM_NO_TRIAL_HELPERS=1 at creation: off)
   int value_first = 1;           // launches without a tape: the first trial after a Newton step evaluates the residual only where the previous sub-step converged in one step (tsim_set_option TSIM_OPT_VALUE_FIRST; TSIM_NO_VALUE_FIRST=1 at creation: off)
   // A/B switches of the environment, read ONCE at creation (launches are on the host-bound path of the per-step collectors):
   // TSIM_NO_EPISODE_LPT, TSIM_INKERNEL_READOUT, TSIM_NO_FREE_RUN, TSIM_LOCKSTEP, TSIM_TAXELS_PER_RECORD, TSIM_NO_ENVTAB_CPT
-  bool ab_no_episode_lpt = false, ab_inkernel_readout = false, ab_no_free_run = false, ab_lockstep = false, ab_taxels_per_record = false, ab_no_envtab_cpt = false, ab_no_default_opts = false; int ab_bwd_lpe = 0, ab_lpt_deal = 2;
+  bool ab_no_episode_lpt = false, ab_inkernel_readout = false, ab_no_free_run = false, ab_lockstep = false, ab_taxels_per_record = false, ab_no_envtab_cpt = false, ab_no_default_opts = false, ab_inkernel_frame_out = false; int ab_bwd_lpe = 0, ab_lpt_deal = 2;
   int pair_cull = 1;             // phase 2 skips contact pairs out of reach of their primitive (tsim_set_option TSIM_OPT_PAIR_CULL; TSIM_NO_PAIR_CULL=1 at creation: off)
   // Compiled-in models (csrc/tsim_static.h).  static_id: the model whose STRUCTURE the batch's blob has (ints + the structural floats: 1 TactilePush);
   // static_exact: every float record equals the compiled asset's bit for bit as well (the fully static instantiation); env_struct_ok: the
@@ -879,11 +880,35 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   a.free_run = (defer || !tac_out || b->ntax == 0) && !b->ab_no_free_run;
   a.lockstep = b->ab_lockstep ? 1 : 0;
   if (a.lockstep) a.free_run = 0;
-  const TsPlan plan = ts_plan(b, TS_K_FORWARD, false, 0);
+  TsPlan plan = ts_plan(b, TS_K_FORWARD, false, 0);
   if (b->record && !plan.fused) b->tape_k_ok = 0;      // records without K from here on
+  // Episode launches of a fused compiled-in model that record a tape, run free and defer the tactile read-out end no frame inside k_forward: a frame's
+  // final state is on the tape, and k_frame_records writes q, qd, the variables and the frame's pose records from it afterwards, on every SIMD, instead
+  // of the launch's slowest wavefront doing it once per slot and frame (k_forward, end of a frame).  The same bits (ts_frame_outputs).  With every
+  // option at its default the forward kernel is k_forward_fr, which has the switch as a constant (TsFrameRecords<>, tsim_static.h: k_forward 2.95 -> 2.57 ms
+  // per 20-step launch, against 2.71 ms with the run-time switch; the pass itself 0.07 ms; profiles/r14_frame_records.md).
+  // TSIM_INKERNEL_FRAME_OUT=1 at creation keeps the in-kernel frame end: A/B, and what tests/test_gpu_frame_records.py compares with.
+  const TsPlan fr_plan = ts_plan(b, TS_K_FRAME_RECORDS, false, 0);
+  // (not in a launch that leaves the pose records of its FINAL state, `emit`: those are taken from the link records the last frame end left in LDS)
+  const bool frame_rec = defer && a.free_run && b->record && nframes > 1 && plan.fused && !emit && !b->ab_inkernel_frame_out &&
+                         fr_plan.variant == plan.variant && fr_plan.lpe == plan.lpe;
+  a.frame_rec = frame_rec ? 1 : 0;
+  plan.frame_rec = frame_rec;
+  b->last_frame_rec = !frame_rec ? 0 : (plan.frame_rec && plan.default_opts) ? 2 : 1;
   { KtScope kt_(b, TSIM_KT_FORWARD, st); if (!ts_launch<false, R>(plan, st, a)) return fail("no k_forward instantiation for the launch plan"); }
   HIPCHK(hipGetLastError());
-  if (defer) { KtScope kt_(b, TSIM_KT_TAXELS, st); if (launch_taxels<R>(b, b->fposeR, b->fposeD, nframes, tac_slot, tac_out, st)) return 1; }
+  if (defer) {
+    KtScope kt_(b, TSIM_KT_TAXELS, st);
+    if (frame_rec) {
+      // about one block per SIMD: the blocks of a chunk cover the environments, the chunks the frames
+      TsPlan p = fr_plan;
+      const int nblk = (int)p.grid, chunks = std::max(1, std::min(nframes, b->n_simd / std::max(nblk, 1))), fpc = (nframes + chunks - 1) / chunks;
+      p.grid = (unsigned)(nblk * ((nframes + fpc - 1) / fpc));
+      if (!ts_launch<false, R>(p, st, a, fpc)) return fail("no k_frame_records instantiation for the launch plan");
+      HIPCHK(hipGetLastError());
+    }
+    if (launch_taxels<R>(b, b->fposeR, b->fposeD, nframes, tac_slot, tac_out, st)) return 1;
+  }
   b->pose_valid = emit ? 1 : 0;
   if (b->B >= 256) {
     const int ns = TS_WAVE / plan.lpe, nsv = (b->B % ns == 0) ? ns : 1;
@@ -1008,6 +1033,7 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   if (const char* e = getenv("TSIM_BWD_LPE")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) b->ab_bwd_lpe = v; }
   b->ab_taxels_per_record = getenv("TSIM_TAXELS_PER_RECORD") != nullptr; b->ab_no_envtab_cpt = getenv("TSIM_NO_ENVTAB_CPT") != nullptr;
   b->value_first = getenv("TSIM_NO_VALUE_FIRST") ? 0 : 1;
+  b->ab_inkernel_frame_out = getenv("TSIM_INKERNEL_FRAME_OUT") != nullptr;
   if (const char* e = getenv("TSIM_VALUE_TRIALS")) b->value_trials = std::max(0, atoi(e));
   if (const char* e = getenv("TSIM_LPE")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) b->lpe_forced = v; }
   b->cross_kinks = dtype == TSIM_F32 ? 1 : 0;
@@ -1114,6 +1140,7 @@ int tsim_get_option(const tsim_batch* b, int option) {
   if (option == TSIM_OPT_CROSS_KINKS) return b->cross_kinks;
   if (option == TSIM_OPT_EVAL_BUDGET) return b->eval_budget;
   if (option == TSIM_OPT_ALL_DEFAULT) return default_options(b) ? 1 : 0;
+  if (option == TSIM_OPT_FRAME_RECORDS) return b->last_frame_rec;
   return -1;
 }
 int tsim_set_solver_options(tsim_batch* b, int cross_kinks, int eval_budget) {

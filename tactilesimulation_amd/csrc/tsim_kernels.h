@@ -119,7 +119,46 @@ template <class R> struct FwdArgs {
   int default_opts = 0;        // every option above is at its default (cross_kinks 1, eval_budget 0, vo_ls 2, vo_first 1, helpers 1, lockstep 0): the launcher of a
                                // compiled-in model may then pick the TsDefaultOpts<> instantiation, which has them as constants (tsim_static.h)
   int helpers = 0;             // slots that have finished their environment evaluate the NEXT line-search trials of a slot that is still in one (k_forward, main loop; TSIM_OPT_TRIAL_HELPERS)
+  int frame_rec = 0;           // fused static instantiations: the frames' outputs (q, qd, variables, pose records) are written after the launch, from the tape, by
+                               // k_frame_records (below); a slot that ends a frame only moves on to the next one (tsim_hip.hip launch_forward)
 };
+
+// The outputs of the frame f that environment env has just finished — the final state in c.qD / c.qd (the link sweep) and c.q0D / c.qd0 (q, qd) —:
+// q, qd, the variables and either the tactile frame (in-kernel read-out) or the frame's pose records for k_taxels.  frame_end / valid are per slot,
+// everything else is wave-uniform where the loops below need it (readout).  One function for its two callers — k_forward at the end of a frame
+// and k_frame_records, which rebuilds the state from the tape — so that both leave the same bits.
+template <int LPE, class R, class MS>
+__device__ __forceinline__ void ts_frame_outputs(const Ctx<R>& c, const FwdArgs<R>& a, int lane, int env, int f, int tslot, bool frame_end, bool valid) {
+  const int nr = c.nr;
+  // the fused static evaluation leaves no link records in LDS: write those of the frame's final state now (what the read-out reads)
+  if constexpr (ts_static_fused<MS, R>()) { if (frame_end) ts_static_value_records<R, MS>(c, lane); }
+  if (frame_end && lane < nr && valid) {
+    const size_t o = ((size_t)f * a.B + env) * nr + lane;
+    if (a.q_out) a.q_out[o] = (R)c.q0D[lane];        // the double position rounded once (== tsim_get_state)
+    if (a.qd_out) a.qd_out[o] = c.qd0[lane];
+  }
+  const bool tac_here = a.tac_out != nullptr && !a.fposeR;       // in-kernel read-out: wave-uniform, and so are f and tslot then (!free_run)
+  readout<LPE>(c, lane, env, frame_end && valid, frame_end && valid && tslot >= 0, a.var_out != nullptr, tac_here && tslot >= 0,
+               a.var_out ? a.var_out + (size_t)f * a.B * 3 * c.nvar : nullptr,
+               (tac_here && tslot >= 0) ? a.tac_out + (size_t)tslot * a.B * 3 * c.ntax : nullptr);
+  if (a.fposeR && frame_end && tslot >= 0) {                     // deferred read-out: this frame's pose records (as k_readout leaves them)
+    int k = 0;
+    for (int sn = 0; sn < c.nsensor; ++sn) {
+      const int* si = c.I + c.off_sensor + sn * TSIM_SI_SIZE;
+      const int nsp = ts_u(si[TSIM_SI_NSPRIM]), sp0 = ts_u(si[TSIM_SI_SPRIM0]);
+      for (int j = 0; j < nsp; ++j, ++k) {
+        TS_SYNC();
+        pair_stage_value(c, ts_u(c.I[c.off_sprim + sp0 + j]), 0, lane == 0);
+        TS_SYNC();
+        const size_t rec = ((size_t)f * a.B + env) * a.nspt + k;
+        if (valid) {
+          for (int e = lane; e < TP_R_SIZE; e += LPE) a.fposeR[rec * TP_R_SIZE + e] = c.PP[e];
+          if (lane < TP_D_SIZE) a.fposeD[rec * TP_D_SIZE + lane] = c.PPd[lane];
+        }
+      }
+    }
+  }
+}
 
 // -DTS_WAVES_PER_EU=n (A/B builds): ask the compiler for n wavefronts per SIMD in the two simulation kernels (2 -> at most 256 registers)
 #define TS_UNLIKELY(x) __builtin_expect(!!(x), 0)      // cold code: laid out behind the loop's straight-line path
@@ -131,14 +170,20 @@ template <class R> struct FwdArgs {
 // (round 6: the adjoint kernel with the model's sizes folded fits 220 registers and ran 18 % slower than the 280-register one until this attribute)
 #define TS_KLB __launch_bounds__(TS_WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
 #endif
-template <class R, int NRM, bool EXPJ, int LPE, bool POLICY = false, class MS = void>
-__global__ void TS_KLB k_forward(FwdArgs<R> a) {
+// the body of k_forward and of k_forward_fr (below): one source, inlined into each kernel
+template <class R, int NRM, bool EXPJ, int LPE, bool POLICY, class MS>
+__device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   R* lds = reinterpret_cast<R*>(smem_raw);
   constexpr int NS = TS_WAVE / LPE;
   // a TsDefaultOpts<> instantiation (tsim_static.h): the options below are their defaults, as constants — the host launches it only then
   constexpr bool kFixed = TsHasDefaultOpts<MS>::value;
 #define TS_OPT(field, fixed) (kFixed ? (fixed) : a.field)
+  // a TsFrameRecords<> instantiation (tsim_static.h): a free-running launch that records a tape and ends no frame in the kernel (a.frame_rec as a
+  // constant) — no output pointer, no pose buffer, no read-out code in it; what the host guarantees of such a launch is a constant too
+  constexpr bool kFrameRec = TsHasFrameRecords<MS>::value;
+  static_assert(!kFrameRec || (!POLICY && ts_static_fused<MS, R>()), "TsFrameRecords<>: fused static models, open loop");
+#define TS_RECORD (kFrameRec ? 1 : a.record)
   const int slot = threadIdx.x / LPE, lane = threadIdx.x % LPE;       // lane: inside the slot
   // Stragglers set the kernel time (all environments wait for the one with the most Newton work), so environments that
   // were expensive in the previous env-step are dispatched first: slot s of block b runs environment order[b NS + s]
@@ -163,9 +208,9 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
   // BDF2 history (the state before the previous sub-step).  While recording it is tape record t0 - 1 — so taped sub-step t is a BDF2
   // step exactly when t >= 2, which is what the adjoint kernel assumes (also after the tape was swapped by the backward cache);
   // without a tape it is the batch's `prev` buffer.
-  bool has_prev = a.record ? a.t0 >= 1 : a.has_prev != 0;
+  bool has_prev = TS_RECORD ? a.t0 >= 1 : a.has_prev != 0;
   if (bdf2_model && has_prev && lane < nr) {
-    if (a.record) {
+    if (TS_RECORD) {
       const R* pr = a.tape + ((size_t)(a.t0 - 1) * a.B + env) * REC;
       c.qm1D[lane] = rec_q(pr)[lane]; c.qm1[lane] = (R)c.qm1D[lane]; c.qdm1[lane] = pr[rec_qd<R>(nr) + lane];
     } else {
@@ -192,7 +237,7 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
 #ifdef TS_PP_TIME      // A/B builds only: share of the launch spent in the policy call, left in gnorm (tools/closed_loop_breakdown.py)
   long long pp_cycles_ = 0; const long long pp_t0_ = clock64();
 #endif
-  const bool free_run = !POLICY && a.free_run != 0 && (a.tac_out == nullptr || a.fposeR != nullptr);
+  const bool free_run = kFrameRec || (!POLICY && a.free_run != 0 && (a.tac_out == nullptr || a.fposeR != nullptr));
   int f = 0, s = 0, tslot = 0;
   bool done = a.nframes <= 0;
   bool fs = !done, ss = !done;               // this slot is at the start of a frame (fetch the action) / of a sub-step (predictor)
@@ -222,7 +267,7 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
   // (reductions inside a slot are symmetric), so iterates, convergence flags, taped matrices and `evals` (trial points judged) are those of
   // the loop without helpers, bit for bit (tests/test_gpu_exact_options.py); a line search of n trials takes ceil(n / (1 + helpers)) rounds.
   // Not in launches that leave their final link records for tsim_readout (a helper's records are not its environment's).
-#define helpers_on (NS > 1 && !POLICY && TS_OPT(helpers, 1) != 0 && !TS_OPT(lockstep, 0) && a.poseR == nullptr)      /* (re-read from the kernel arguments where it is asked: no register held for it) */
+#define helpers_on (NS > 1 && !POLICY && TS_OPT(helpers, 1) != 0 && !TS_OPT(lockstep, 0) && (kFrameRec || a.poseR == nullptr))      /* (re-read from the kernel arguments where it is asked: no register held for it) */
   static_assert(NS <= 4, "helper slots: three result registers (gh0..gh2) and step factors 1/2, 1/4, 1/8 — at most three helpers per owner");
   if (helpers_on && !valid) { done = true; fs = false; ss = false; }      // an idle slot of the last wavefront helps from the start
   int helped = 0;
@@ -235,13 +280,14 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
   // needs H from it, and free-running slots drift out of phase (one at its predictor while the other is at its trial: every round full); a slot
   // about to START a sub-step therefore waits ONE round — at most once per sub-step — when that makes the round value-only, which puts it in
   // phase with the others.  Same iterates, flags and evaluation counts as without the option (tests/test_gpu_exact_options.py).
-  const bool vfirst = TS_OPT(vo_first, 1) != 0 && a.record == 0 && !POLICY && !TS_OPT(lockstep, 0);
+  const bool vfirst = TS_OPT(vo_first, 1) != 0 && TS_RECORD == 0 && !POLICY && !TS_OPT(lockstep, 0);
   // `kq`: the last measured contraction of a full Newton step of this slot, ||g_new|| / ||g||^2 (quadratic convergence: roughly a constant of
   // the problem) — the first trial after a step from residual gn is expected to end the sub-step if kq gn^2 is well below tol.
   R kq = R(1e30);
   bool waited = false;
 #ifdef TS_ROUND_STATS   // A/B builds only (tools/round_stats.py): rounds of this wavefront and its shader clocks, left in status / gnorm
   int rounds_ = 0; const long long rs_t0_ = clock64();
+  int fe_execs_ = 0; long long fe_cycles_ = 0;      // the frame-end block: times this wavefront ran it and the shader clocks it spent there, left in helped
 #endif
   while (!__all(done)) {
 #ifdef TS_ROUND_STATS
@@ -272,7 +318,7 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
       }
       // a NaN / inf control would be clamped away silently by the motor law's fmin / fmax: flag it (status bit 30) instead
       if (seg_sum<LPE>(ts_finite(uv) ? R(0) : R(1)) > R(0)) nonfinite = true;
-      tslot = a.tac_slot ? a.tac_slot[f] : f;      // used at the end of the frame: fetched here, the load is long done by then
+      if constexpr (!kFrameRec) tslot = a.tac_slot ? a.tac_slot[f] : f;      // used at the end of the frame: fetched here, the load is long done by then
       fs = false;
     }
     bool wait_ = false;                        // this slot sits this round out (see `vfirst` above): it re-evaluates its last point, nothing is judged
@@ -401,7 +447,7 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
         // A launch that records no tape has no use for H of a point that ENDS the sub-step: this slot's own value-only evaluation of such a
         // point is taken as it is, a helper's is evaluated again by this slot (its link records are the frame's) — value-only.
         const bool ends = !ts_finite(gj) || gj < c.tol || (ls >= 0 && iter + 1 >= c.max_iter) || (TS_OPT(eval_budget, 0) > 0 && sub_evals + 1 >= TS_OPT(eval_budget, 0));
-        const bool no_h = ends && a.record == 0;
+        const bool no_h = ends && TS_RECORD == 0;
         bool usable = j == 0 ? (tang || no_h) : (tang && !ends);
         vo = !usable && no_h && (TS_OPT(vo_ls, 2) > 0 || vfirst);
         if (usable) {
@@ -471,7 +517,7 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
     if (commit) {
       if (!conv) ++bad;
       gmax = t_max(gmax, gn);
-      if (a.record && valid) {
+      if (TS_RECORD && valid) {
         R* rec = a.tape + ((size_t)(a.t0 + f * a.nsub + s + 1) * a.B + env) * REC;
         if (lane < nr) { rec_q(rec)[lane] = c.qD[lane]; rec[rec_qd<R>(nr) + lane] = c.qd[lane]; }
         for (int e = lane; e < nr * nr; e += LPE) rec[rec_H<R>(nr) + e] = c.H[e];
@@ -492,41 +538,24 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
     TS_SYNC();
     // ---- end of a frame (per slot in a free-running launch, all slots together otherwise): the link poses / velocities in LDS are
     //      those of the accepted state (last evaluation)
-    if (TS_UNLIKELY(__any(frame_end))) {       // once per frame and slot: kept out of the loop's straight-line code
-      // the fused static evaluation leaves no link records in LDS: write those of the frame's final state now (what the read-out reads)
-      if constexpr (ts_static_fused<MS, R>()) { if (frame_end) ts_static_value_records<R, MS>(c, lane); }
-      if (frame_end && lane < nr && valid) {
-        const size_t o = ((size_t)f * a.B + env) * nr + lane;
-        if (a.q_out) a.q_out[o] = (R)c.q0D[lane];        // the double position rounded once (== tsim_get_state)
-        if (a.qd_out) a.qd_out[o] = c.qd0[lane];
-      }
-      const bool tac_here = a.tac_out != nullptr && !a.fposeR;       // in-kernel read-out: wave-uniform, and so are f and tslot then (!free_run)
-      readout<LPE>(c, lane, env, frame_end && valid, frame_end && valid && tslot >= 0, a.var_out != nullptr, tac_here && tslot >= 0,
-                   a.var_out ? a.var_out + (size_t)f * a.B * 3 * c.nvar : nullptr,
-                   (tac_here && tslot >= 0) ? a.tac_out + (size_t)tslot * a.B * 3 * c.ntax : nullptr);
-      if (a.fposeR && frame_end && tslot >= 0) {                     // deferred read-out: this frame's pose records (as k_readout leaves them)
-        int k = 0;
-        for (int sn = 0; sn < c.nsensor; ++sn) {
-          const int* si = c.I + c.off_sensor + sn * TSIM_SI_SIZE;
-          const int nsp = ts_u(si[TSIM_SI_NSPRIM]), sp0 = ts_u(si[TSIM_SI_SPRIM0]);
-          for (int j = 0; j < nsp; ++j, ++k) {
-            TS_SYNC();
-            pair_stage_value(c, ts_u(c.I[c.off_sprim + sp0 + j]), 0, lane == 0);
-            TS_SYNC();
-            const size_t rec = ((size_t)f * a.B + env) * a.nspt + k;
-            if (valid) {
-              for (int e = lane; e < TP_R_SIZE; e += LPE) a.fposeR[rec * TP_R_SIZE + e] = c.PP[e];
-              if (lane < TP_D_SIZE) a.fposeD[rec * TP_D_SIZE + lane] = c.PPd[lane];
-            }
-          }
-        }
-      }
+    if constexpr (kFrameRec) {
+      // nothing of a frame's end is done here: its final state is tape record t0 + (f + 1) nsub, and k_frame_records writes the outputs from it
+      if (frame_end) { ++f; fs = true; if (f == a.nframes) { done = true; fs = false; ss = false; } }
+    } else if (TS_UNLIKELY(__any(frame_end))) {       // once per frame and slot: kept out of the loop's straight-line code
+#ifdef TS_ROUND_STATS
+      ++fe_execs_; const long long fe_t0_ = clock64();
+#endif
+      // (a.frame_rec — the fused static instantiations, the run-time form of TsFrameRecords<> —: the outputs are left to k_frame_records)
+      if (!(ts_static_fused<MS, R>() && !POLICY && a.frame_rec != 0)) ts_frame_outputs<LPE, R, MS>(c, a, lane, env, f, tslot, frame_end, valid);
       if (frame_end) { ++f; fs = true; if (f == a.nframes) { done = true; fs = false; ss = false; } }
       TS_SYNC();
+#ifdef TS_ROUND_STATS
+      fe_cycles_ += clock64() - fe_t0_;
+#endif
     }
   }
-  if constexpr (ts_static_fused<MS, R>()) { if (a.poseR && a.nframes <= 0) ts_static_value_records<R, MS>(c, lane); }
-  if (a.poseR) {
+  if constexpr (ts_static_fused<MS, R>() && !kFrameRec) { if (a.poseR && a.nframes <= 0) ts_static_value_records<R, MS>(c, lane); }
+  if (!kFrameRec && a.poseR) {
     // Large pads are read out on demand (tsim_readout), by a kernel whose lanes are taxels and which needs, per (sensor, primitive)
     // combination, the pose of the sensor link in the primitive's frame and the relative twist there.  The link records in LDS are those
     // of the state this launch ends in: leave the pose records here and the read-out needs no kinematics kernel of its own.
@@ -548,7 +577,7 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
   }
   if (valid) {
     if (bdf2_model && lane < nr) { a.prev[(size_t)env * 2 * nr + lane] = c.qm1D[lane]; a.prev[(size_t)env * 2 * nr + nr + lane] = (double)c.qdm1[lane]; }
-    if (!a.record) {
+    if (!TS_RECORD) {
       R* st = a.tape + ((size_t)a.t0 * a.B + env) * REC;
       if (lane < nr) { rec_q(st)[lane] = c.q0D[lane]; st[rec_qd<R>(nr) + lane] = c.qd0[lane]; }
     }
@@ -561,11 +590,58 @@ __global__ void TS_KLB k_forward(FwdArgs<R> a) {
 #endif
 #ifdef TS_ROUND_STATS
     if (lane == 0) { if (a.gnorm) a.gnorm[env] = (float)(clock64() - rs_t0_); if (a.status) a.status[env] = rounds_; }
+    if (lane == 0 && a.helped) a.helped[env] = (int)(fe_cycles_ < (1ll << 23) - 1 ? fe_cycles_ : (1ll << 23) - 1) * 256 + (fe_execs_ < 255 ? fe_execs_ : 255);
 #endif
   }
 }
 #undef helpers_on
 #undef TS_OPT
+#undef TS_RECORD
+template <class R, int NRM, bool EXPJ, int LPE, bool POLICY = false, class MS = void>
+__global__ void TS_KLB k_forward(FwdArgs<R> a) { ts_forward<R, NRM, EXPJ, LPE, POLICY, MS>(a); }
+// ... with every option at its default AND no frame end in the kernel, as constants (TsFrameRecords<TsDefaultOpts<MS>>, tsim_static.h).  A kernel of its
+// own name: the instantiations of k_forward are a pinned list (tests/test_capi_symbols.py), and the bench's `kernel` record names k_forward's
+template <class R, int NRM, int LPE, class MS>
+__global__ void TS_KLB k_forward_fr(FwdArgs<R> a) { ts_forward<R, NRM, false, LPE, false, TsFrameRecords<TsDefaultOpts<MS>>>(a); }
+
+// The frames' outputs of a launch that ended no frame in the kernel (a.frame_rec, TsFrameRecords<>), written AFTER k_forward from the tape it left.
+// Frame f of environment e ends in tape record t0 + (f + 1) nsub: q as double, qd — what the link sweep at the end of a frame reads from LDS (the
+// accelerations enter no output: zero here, as in k_readout) — so q, qd, the variables and the frame's pose records are functions of data that is in
+// memory anyway, and ts_frame_outputs gives them the bits the in-kernel frame end gives them.  In k_forward that code runs on the launch's critical
+// wavefront, once per slot and frame with the other slots masked; here every SIMD of the device takes part.  Same 16 / 32 / 64 lanes per environment
+// and the same LDS layout as the forward launch; a slot keeps ITS environment (environment index = slot index: k_forward's order does not apply)
+// and walks a.nframes in chunks of fpc frames (blockIdx.x / blocks-per-chunk: the chunk), so the model tables — per environment with
+// tsim_set_env_tables — are staged once per block, not once per record.
+// (One wavefront per SIMD, as the forward launch: its LDS footprint allows no more, and without the attribute this compiler's register allocator crashes on the kernel.)
+template <class R, int LPE, class MS>
+__global__ void TS_KLB k_frame_records(FwdArgs<R> a, int fpc) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  R* lds = reinterpret_cast<R*>(smem_raw);
+  constexpr int NS = TS_WAVE / LPE;
+  const int slot = threadIdx.x / LPE, lane = threadIdx.x % LPE;
+  const int nblk = (a.B + NS - 1) / NS, chunk = blockIdx.x / nblk;
+  const int eidx = (blockIdx.x - chunk * nblk) * NS + slot;
+  const bool valid = eidx < a.B;
+  const int env = min(eidx, a.B - 1);
+  Ctx<R> c; ctx_init<R, MS>(c, a.I, a.F, lds, NS, slot, lane, LPE, false, a.Fenv ? a.Fenv + (size_t)env * a.fstride : nullptr);      // (no contact points: nothing here reads them)
+  const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R), a.tk);
+  init_world(c, lane, LPE);
+  const int f0 = chunk * fpc, f1 = min(f0 + fpc, a.nframes);
+  // a frame's state is fetched one frame ahead: a lone wavefront cannot hide the load
+  double qn = 0.0; R qdn = R(0);
+  const R* st = a.tape + ((size_t)(a.t0 + (f0 + 1) * a.nsub) * a.B + env) * REC;
+  const size_t frame_stride = (size_t)a.nsub * a.B * REC;
+  if (f0 < f1 && lane < nr) { qn = rec_q(st)[lane]; qdn = st[rec_qd<R>(nr) + lane]; }
+  for (int f = f0; f < f1; ++f) {
+    const int tslot = a.tac_slot ? a.tac_slot[f] : f;
+    TS_SYNC();
+    if (lane < nr) { c.qD[lane] = qn; c.q0D[lane] = qn; c.q[lane] = (R)qn; c.qd[lane] = qdn; c.qd0[lane] = qdn; c.qa[lane] = R(0); }
+    st += frame_stride;
+    if (f + 1 < f1 && lane < nr) { qn = rec_q(st)[lane]; qdn = st[rec_qd<R>(nr) + lane]; }
+    TS_SYNC();
+    ts_frame_outputs<LPE, R, MS>(c, a, lane, env, f, tslot, true, valid);
+  }
+}
 
 
 // ================================================================================================ backward kernel

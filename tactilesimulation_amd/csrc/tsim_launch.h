@@ -1,7 +1,7 @@
 // tsim_launch.h — launch plans of the simulation kernels and the one launcher that runs them.
 //
 // A plan (TsPlan, made by tsim_hip.hip ts_plan and nowhere else) names one instantiation of k_forward, k_backward, k_backward_z, k_debug_eval,
-// k_param_grad or k_param_grad_body and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
+// k_frame_records, k_param_grad or k_param_grad_body and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
 // (tsim_hip.hip; the parameter passes: tsim_param_grad.hip, tsim_param_grad_body.hip), or a compiled-in model (tsim_static.h), whose translation units hold nothing but the
 // explicit instantiations of TsLaunch for their view: they are built with flags of their own (host/buildhash.py HIP_UNITS).
 #pragma once
@@ -10,7 +10,7 @@
 #include "tsim_param_grad.h"
 #include "tsim_static_pusher.h"
 
-enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD, TS_K_PARAM_GRAD_BODY };
+enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD, TS_K_PARAM_GRAD_BODY, TS_K_FRAME_RECORDS };
 // the view of a launch: the generic kernels, a compiled-in model fully static, or its structure-static twin (parameters at run time)
 enum { TS_KM_GENERIC = 0, TS_KM_STATIC = 1, TS_KM_PARAM = 2 };
 using TsParamPusher = TsParam<TsStaticPusher>;
@@ -20,6 +20,7 @@ struct TsPlan {
   int nrm = 8; bool expj = false; int lpe = TS_WAVE;      // rows of the register solve, rotation-vector joint compiled in, lanes per environment
   bool policy = false;                                    // the TactilePush policy between the frames (tsim_policy_push.h)
   bool default_opts = false;                              // every option at its default: the TsDefaultOpts<> instantiation (tsim_static.h)
+  bool frame_rec = false;                                 // ... and no frame ends in the kernel: k_forward_fr (set by launch_forward for such a launch)
   unsigned grid = 0; size_t lds = 0;
   bool fused = false;      // the view's model is FUSED (ts_static_fused): its forward writes K next to H on the tape, its adjoint reads it
 };
@@ -31,11 +32,11 @@ template <class MS> constexpr int ts_view_nrm() { return ts_static_nr<MS>() == 0
 // (tests/test_capi_symbols.py pins the set).  Every view: NRM 8 / 16 at 16 / 32 / 64 lanes per environment, a rotation-vector joint only at NRM 16
 // and 64 lanes; the closed loop: TactilePush's forward and adjoint (NRM 8).  A compiled-in model (ms_nrm != 0): its own NRM, no parameter pass;
 // fp64 not at 16 lanes (four environments' LDS is over the cap); the closed loop and the debug kernel at fp32 and 16 lanes only; the TsDefaultOpts<>
-// twin of the forward kernel at fp32 and 16 lanes.
+// twin of the forward kernel at fp32 and 16 lanes, and there its k_forward_fr twin; k_frame_records wherever a FUSED compiled-in model has a forward kernel.
 constexpr bool ts_instantiated(int kernel, int ms_nrm, bool fp32, bool policy, bool default_opts, int nrm, bool expj, int lpe) {
   if ((expj && (nrm != 16 || lpe != 64)) || (nrm != 8 && nrm != 16) || (lpe != 16 && lpe != 32 && lpe != 64)) return false;
   if (policy && (nrm != 8 || expj || (kernel != TS_K_FORWARD && kernel != TS_K_BACKWARD))) return false;
-  if (ms_nrm == 0) return !default_opts;
+  if (ms_nrm == 0) return !default_opts && kernel != TS_K_FRAME_RECORDS;
   if (kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || nrm != ms_nrm || expj) return false;
   if (default_opts) return kernel == TS_K_FORWARD && fp32 && lpe == 16;
   if (policy || kernel == TS_K_DEBUG_EVAL) return fp32 && lpe == 16;
@@ -64,6 +65,7 @@ template <class MS, bool POLICY, class R> struct TsLaunch {
     return p.nrm == 8 ? lanes(TsInt<8>(), TsBool<false>()) : p.nrm == 16 && lanes(TsInt<16>(), TsBool<false>());
   }
   static bool run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a);
+  static bool run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a, int fpc);      // k_frame_records (TS_K_FRAME_RECORDS): fpc frames per block
   static bool run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave = nullptr);      // zsave: k_backward_z (TS_K_BACKWARD_Z)
   static bool run(const TsPlan& p, hipStream_t st, const DbgArgs<R>& a);
   static bool run(const TsPlan& p, hipStream_t st, const PgArgs<R>& a);
@@ -73,10 +75,18 @@ template <class MS, bool POLICY, class R> struct TsLaunch {
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a) {
   return shape<TS_K_FORWARD>(p, [&](auto nrm, auto expj, auto lpe) {
     if constexpr (ts_instantiated(TS_K_FORWARD, ts_view_nrm<MS>(), sizeof(R) == 4, POLICY, true, nrm, expj, lpe)) {
+      if (p.default_opts && p.frame_rec) {
+        if constexpr (!POLICY && ts_static_fused<MS, R>()) { hipLaunchKernelGGL((k_forward_fr<R, nrm, lpe, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); return; }
+      }
       if (p.default_opts) { hipLaunchKernelGGL((k_forward<R, nrm, expj, lpe, POLICY, TsDefaultOpts<MS>>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); return; }
     }
     hipLaunchKernelGGL((k_forward<R, nrm, expj, lpe, POLICY, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a);
   });
+}
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a, int fpc) {
+  if constexpr (!POLICY && ts_static_fused<MS, R>())
+    return shape<TS_K_FRAME_RECORDS>(p, [&](auto, auto, auto lpe) { hipLaunchKernelGGL((k_frame_records<R, lpe, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a, fpc); });
+  else return false;
 }
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave) {
   if (p.kernel == TS_K_BACKWARD_Z)

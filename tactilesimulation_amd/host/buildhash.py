@@ -141,7 +141,7 @@ def write_kernel_table(lib=None, out=None):
 
 
 def kernel_name(kernel, dtype, nr, has_exp, lanes, variant, policy=False, default_opts=False):
-    """Mangled name of the instantiation of k_forward / k_backward a batch launches (csrc/tsim_hip.hip ts_plan) and a readable form of it.
+    """Mangled name of the instantiation of k_forward / k_backward / k_frame_records / k_forward_fr a batch launches (csrc/tsim_hip.hip ts_plan) and a readable form of it.
     default_opts: every solver / scheduling option of the batch is at its default (tsim_get_option TSIM_OPT_ALL_DEFAULT): the fp32 forward launch of a
     compiled-in model at 16 lanes per environment then runs the TsDefaultOpts<> instantiation (csrc/tsim_static.h)."""
     nrm, expj, lpe = (16, True, 64) if has_exp else ((8 if nr <= 8 else 16), False, lanes)
@@ -151,6 +151,13 @@ def kernel_name(kernel, dtype, nr, has_exp, lanes, variant, policy=False, defaul
     if default_opts and kernel == "k_forward" and variant != "generic" and dtype == "f32" and lpe == 16:
         ms = ("13TsDefaultOptsI%sE" % ms[0], "TsDefaultOpts<%s>" % ms[1])
     r = {"f32": ("f", "float"), "f64": ("d", "double")}[dtype]
+    # the two kernels of an episode launch that ends no frame inside the forward kernel (csrc/tsim_hip.hip launch_forward; fused compiled-in models):
+    # k_frame_records, the pass that writes the frames' outputs from the tape, at every shape the view's k_forward has; k_forward_fr, the forward
+    # kernel with that switch and every option's default as constants, where the TsDefaultOpts<> twin is (fp32, 16 lanes)
+    if kernel == "k_frame_records":
+        return ("_Z15k_frame_recordsI%sLi%dE%sEv7FwdArgsIT_Ei" % (r[0], lpe, ms[0]), "k_frame_records<%s, LPE=%d, %s>" % (r[1], lpe, ms[1]))
+    if kernel == "k_forward_fr":
+        return ("_Z12k_forward_frI%sLi%dELi%dE%sEv7FwdArgsIT_E" % (r[0], nrm, lpe, ms[0]), "k_forward_fr<%s, NRM=%d, LPE=%d, %s>" % (r[1], nrm, lpe, ms[1]))
     args = {"k_forward": "7FwdArgs", "k_backward": "7BwdArgs"}[kernel]
     mangled = "_Z%d%sI%sLi%dELb%dELi%dELb%dE%sEv%sIT_E" % (len(kernel), kernel, r[0], nrm, int(expj), lpe, int(policy), ms[0], args)
     return mangled, "%s<%s, NRM=%d, EXPJ=%s, LPE=%d, POLICY=%s, %s>" % (kernel, r[1], nrm, str(expj).lower(), lpe, str(policy).lower(), ms[1])

@@ -69,8 +69,9 @@ int tsim_table_size(const tsim_batch* b);
  * sub-step (the same kernel variant, compiled with that store) and a second pass over (environment, chunk of sub-steps) adds the gradient;
  * sums are in a fixed order (bit-identical from run to run).  The entries are those of the environment's row of tsim_set_env_tables, or of
  * the shared model.  The stick / slip switch of the friction law is a kink: these are one-sided derivatives of the smooth piece each contact
- * point is on (tsim_debug_signature).  The first non-NULL call allocates [tape_capacity][B][ndof_r] reals for z.  Not available on the fused
- * closed-loop launches (tsim_push_closed_backward fails while it is set). */
+ * point is on (tsim_debug_signature).  The first non-NULL call allocates [tape_capacity][B][ndof_r] reals for z.  The fused closed-loop
+ * adjoint launch (include/tsim_env.h tsim_push_closed_backward) adds to the buffer in the same way, under the same conventions.
+ * While the buffer is NULL nothing more is launched or allocated by any adjoint launch, and the kernels that run are the ones that ran before. */
 int tsim_set_param_grad(tsim_batch* b, void* dL_dtables);
 
 /* Which groups of table entries tsim_set_param_grad's buffer receives (a mask of TSIM_PG_*; the default, TSIM_PG_CONTACT, is the list above):
@@ -90,6 +91,12 @@ int tsim_set_param_grad(tsim_batch* b, void* dL_dtables);
 enum { TSIM_PG_CONTACT = 1, TSIM_PG_INERTIAL = 2, TSIM_PG_MOTOR = 4, TSIM_PG_LIMIT = 8 };
 int tsim_set_param_grad_groups(tsim_batch* b, int mask);
 int tsim_get_param_grad_groups(const tsim_batch* b);      /* the mask (-1: null batch) */
+
+/* Diagnostics: what the most recent adjoint launch of the batch ran.  out[0]: its kernel (TSIM_ADJ_*; -1: no adjoint launch yet) — k_backward,
+ * its twin that also saves z (a buffer was set: tsim_set_param_grad), or the closed-loop adjoint's twin (tsim_push_closed_backward with a buffer
+ * set); out[1]: the parameter passes launched behind it, bit 0 the contact pass (k_param_grad), bit 1 the body groups' (k_param_grad_body). */
+enum { TSIM_ADJ_BACKWARD = 0, TSIM_ADJ_BACKWARD_Z = 1, TSIM_ADJ_CLOSED_BACKWARD_Z = 2 };
+int tsim_last_adjoint_launch(const tsim_batch* b, int32_t* out);
 
 /* sim.set_state_init(q, qdot) + sim.reset(backward_flag)      envs/redmax_torch_functions.py:39-41,
  * envs/tactile_push_env.py:138,154.  q0 / qd0: [B][ndof_r].  Restarts the tape and zeroes the carried

@@ -71,7 +71,18 @@ int tsim_push_closed_rollout(tsim_batch* b, const tsim_push_policy* pol, const v
  * its direct partial w.r.t. the policy outputs (the reward's action term), the forward records, -> per frame the gradients w.r.t. the layers'
  * pre-activations g1, g2 [T][B][64], g3 [T][B][3] (weight gradients: dW_l = sum_t g_l[t]^T x_l[t], assembled by the caller as batched GEMMs),
  * dobs_tac [T][B][390] (workspace and result: gradient w.r.t. the tactile part of frame f's observation), df_du [T][B][6] or NULL.
- * The dependence of the FIRST observation on the initial state is not propagated (tsim_get_adjoint excludes it). */
+ * The dependence of the FIRST observation on the initial state is not propagated (tsim_get_adjoint excludes it).
+ * With a table-gradient buffer set (include/tsim.h tsim_set_param_grad, groups: tsim_set_param_grad_groups) the launch also ADDS, per environment,
+ * dL/d(table entry) of the episode into the caller's [B][tsim_table_size] buffer: the closed-loop adjoint kernel's twin that saves z of every
+ * sub-step runs instead (the same variant: generic, static:pusher or param:pusher), then the contact pass and / or the body groups' pass over the
+ * num_frames x num_steps sub-steps just undone and their fixed-order reductions, all on `stream` — no host synchronisation, nothing allocated, so
+ * the call stays capturable into a HIP graph.  Conventions, those of the open-loop adjoint launches: the gradient adds (it accumulates over
+ * episodes until the caller zeroes the buffer); only the columns of the enabled groups are touched, every other column keeps its bits; the
+ * entries are those of the environment's row of tsim_set_env_tables, or of the shared model; sums are in a fixed order, bit-identical from run to
+ * run.  The tactile seeds are the policy's own: frame f's tactile output is observed by frame f + 1 (dobs_tac[f + 1]), the last frame's by nobody
+ * (no sensor term), and there is none at all with obs_mode 1 or 2.  tac0 and the first frame's goal / pose part are caller inputs: their
+ * dependence on the parameters is not propagated, like that of the first observation on the initial state.  Buffer not set: nothing new is
+ * launched or allocated, and the kernel is the closed-loop k_backward. */
 int tsim_push_closed_backward(tsim_batch* b, const tsim_push_policy* pol, const void* goal, int num_frames, int num_steps,
                               const void* df_dq, const void* df_dvar, const void* du_direct, const void* u_out, const void* h1_out, const void* h2_out,
                               void* g1_out, void* g2_out, void* g3_out, void* dobs_tac, void* df_du, void* stream);

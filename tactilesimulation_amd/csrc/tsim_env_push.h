@@ -196,16 +196,29 @@ static int push_closed_backward_t(tsim_batch* b, const tsim_push_policy* pol, co
   a.pol.goal = (const R*)goal; a.pol.du_direct = (const R*)du_direct;
   a.pol.u_out = (R*)u_out; a.pol.h1_out = (R*)h1_out; a.pol.h2_out = (R*)h2_out;
   a.pol.g1_out = (R*)g1_out; a.pol.g2_out = (R*)g2_out; a.pol.g3_out = (R*)g3_out; a.pol.dobs_tac = (R*)dobs_tac;
-  if (!ts_launch<true, R>(ts_plan(b, TS_K_BACKWARD, true, 0), st, a)) return fail("no closed-loop k_backward instantiation for the launch plan");
+  // with a table-gradient buffer set (tsim_set_param_grad): the same variant's twin that also saves z of every sub-step, then the parameter passes
+  // over the sub-steps just undone, all on this stream.  Not set: the kernel it always was, and nothing else.
+  if (!ts_launch<true, R>(ts_plan(b, b->dLdp ? TS_K_CLOSED_BACKWARD_Z : TS_K_BACKWARD, true, 0), st, a, (R*)b->zbuf)) return fail("no closed-loop k_backward instantiation for the launch plan");
   HIPCHK(hipGetLastError());
-  return 0;
+  b->adj_kernel = b->dLdp ? TSIM_ADJ_CLOSED_BACKWARD_Z : TSIM_ADJ_BACKWARD;
+  if (!b->dLdp) { b->adj_passes = 0; return 0; }
+  // The contact pass's tactile seeds: frame f's tactile output is what frame f + 1's policy call observed, and the kernel above left its adjoint in
+  // dobs_tac[f + 1] (k_backward reads the same row: tsim_kernels_backward.h); nothing observes the last frame's.  Slot f of the table is row f of
+  // dobs_tac + one row, -1 for the last frame (never dereferenced for it).  Without the tactile observation there is no tactile seed.
+  const R* seeds = nullptr;
+  if (a.pol.mode == TSIM_PUSH_OBS_TACTILE && (b->pg_groups & TS_PG_CONTACT)) {
+    if (nframes > b->cap || !b->pg_slots) return fail("push_closed_backward: the seed table is missing or too small");
+    ts_closed_slots_launch(b->pg_slots, nframes, st);
+    HIPCHK(hipGetLastError());
+    seeds = (const R*)dobs_tac + (size_t)b->B * PP_NTAC;
+  }
+  return launch_param_passes<R>(b, a.n, nsub, 1, seeds ? b->pg_slots : nullptr, seeds, st);
 }
 
 extern "C" int tsim_push_closed_backward(tsim_batch* b, const tsim_push_policy* pol, const void* goal, int num_frames, int num_steps,
                                          const void* df_dq, const void* df_dvar, const void* du_direct, const void* u_out, const void* h1_out, const void* h2_out,
                                          void* g1_out, void* g2_out, void* g3_out, void* dobs_tac, void* df_du, void* stream) {
   if (int rc = push_closed_check(b, pol, num_frames, num_steps, "push_closed_backward")) return rc;
-  if (b->dLdp) return fail("push_closed_backward: the parameter gradient (tsim_set_param_grad) is not available on the fused closed-loop launches; set it to NULL");
   if (!pol->W1p || !pol->W2 || pol->w1_stride < push_obs_len(pol->obs_mode) || pol->w1_stride % 4 || pol->w1_stride > 64 * (int)PP_OCH) return fail("push_closed_backward: W1p [64][w1_stride >= observation length, multiple of 4] and W2 are required");
   if (!b->record) return fail("push_closed_backward: reset(backward_flag=True) was not called");
   const long long n = (long long)num_frames * num_steps;

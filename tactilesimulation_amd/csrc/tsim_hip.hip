@@ -466,6 +466,11 @@ struct tsim_batch {
   // tsim_set_param_grad_groups: which groups of columns a launch adds to (TSIM_PG_*), and the body pass's partial sums
   // [pg_chunks][B][ts_pgb_count] (pg_alloc: once a body group is on and the gradient is asked for)
   int pg_groups = TS_PG_CONTACT; void* pgbpart = nullptr;
+  // the closed-loop adjoint with the buffer set (tsim_push_closed_backward): frame -> seed row of the contact pass, [cap] (pg_alloc; written on the
+  // launch's stream by ts_closed_slots_launch)
+  int32_t* pg_slots = nullptr;
+  // diagnostics (tsim_last_adjoint_launch): the kernel of the most recent adjoint launch (TSIM_ADJ_*, -1: none yet) and the parameter passes behind it
+  int adj_kernel = -1, adj_passes = 0;
   // tsim_kernel_timing: HIP events around every launch of the simulation kernels, on the stream they are launched on
   int kt_on = 0;
   std::vector<KtPair> kt;           // pairs recorded since the last tsim_kernel_times
@@ -780,7 +785,7 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   TsPlan p;
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
-  const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z;
+  const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z || kernel == TS_K_CLOSED_BACKWARD_Z;
   p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
@@ -974,6 +979,23 @@ static int launch_param_grad_body(tsim_batch* b, int n, hipStream_t st) {
                               b->pgbpart, seg, st);
 }
 
+// The passes behind an adjoint launch that saved z (b->dLdp set; nothing otherwise): the contact pass with the launch's seed layout, then the body
+// groups' pass, each only where its groups are on
+template <class R>
+static int launch_param_passes(tsim_batch* b, int n, int seed_stride, int frames, const int32_t* tac_slot, const void* df_dtac, hipStream_t st) {
+  b->adj_passes = 0;
+  if (!b->dLdp) return 0;
+  if (b->pg_groups & TS_PG_CONTACT) {
+    if (launch_param_grad<R>(b, n, seed_stride, frames, tac_slot, df_dtac, st)) return 1;
+    b->adj_passes |= 1;
+  }
+  if (b->pg_groups & ~TS_PG_CONTACT) {
+    if (launch_param_grad_body<R>(b, n, st)) return 1;
+    b->adj_passes |= 2;
+  }
+  return 0;
+}
+
 template <class R>
 static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, const int32_t* tac_slot, const void* df_dq, const void* df_dvar, const void* df_dtac, void* df_du, hipStream_t st) {
   BwdArgs<R> a = bwd_args<R>(b);
@@ -987,9 +1009,8 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
     if (!ts_launch<false, R>(plan, st, a, (R*)b->zbuf)) return fail("no k_backward instantiation for the launch plan");
   }
   HIPCHK(hipGetLastError());
-  if (b->dLdp && (b->pg_groups & TS_PG_CONTACT) && launch_param_grad<R>(b, n, seed_stride, frames, tac_slot, df_dtac, st)) return 1;
-  if (b->dLdp && (b->pg_groups & ~TS_PG_CONTACT)) return launch_param_grad_body<R>(b, n, st);
-  return 0;
+  b->adj_kernel = b->dLdp ? TSIM_ADJ_BACKWARD_Z : TSIM_ADJ_BACKWARD;
+  return launch_param_passes<R>(b, n, seed_stride, frames, tac_slot, df_dtac, st);
 }
 
 extern "C" {
@@ -1073,7 +1094,7 @@ void tsim_batch_destroy(tsim_batch* b) {
   for (auto& k : b->kt) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
   for (hipEvent_t e : b->kt_free) (void)hipEventDestroy(e);
   (void)hipFree(b->dFenv); (void)hipFree(b->dI); (void)hipFree(b->dF); (void)hipFree(b->tape); (void)hipFree(b->lamq); (void)hipFree(b->lamv); (void)hipFree(b->evals); (void)hipFree(b->helped); (void)hipFree(b->gnorm); (void)hipFree(b->order); (void)hipFree(b->order_ep); (void)hipFree(b->prev); (void)hipFree(b->poseR); (void)hipFree(b->poseD); (void)hipFree(b->fposeR); (void)hipFree(b->fposeD); (void)hipFree(b->dKmask); (void)hipFree(b->dFlag);
-  (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); (void)hipFree(b->pgbpart);
+  (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); (void)hipFree(b->pgbpart); (void)hipFree(b->pg_slots);
   delete b;
 }
 
@@ -1228,7 +1249,7 @@ int tsim_table_size(const tsim_batch* b) { return b->nfrec; }
 // and, once a body group is on as well, the body pass's partial sums (the default mask never allocates those).  What is there already stays.
 static int pg_alloc(tsim_batch* b) {
   const bool body = (b->pg_groups & ~TS_PG_CONTACT) != 0;
-  if (b->zbuf && b->pgpart && (b->pgbpart || !body)) return 0;
+  if (b->zbuf && b->pgpart && b->pg_slots && (b->pgbpart || !body)) return 0;
   TS_DEVICE(b);
   const int chunks = pg_layout(b, b->cap).most;
   auto get = [&](void** p, size_t reals) {
@@ -1242,6 +1263,11 @@ static int pg_alloc(tsim_batch* b) {
     return fail("set_param_grad: hipMalloc failed");
   }
   b->pg_chunks = chunks;
+  // ... and the closed-loop adjoint's frame -> seed row table: at most one frame per taped sub-step
+  if (!b->pg_slots && hipMalloc((void**)&b->pg_slots, std::max<size_t>((size_t)b->cap * sizeof(int32_t), 8)) != hipSuccess) {
+    (void)hipGetLastError(); b->pg_slots = nullptr;
+    return fail("set_param_grad: hipMalloc failed");
+  }
   return 0;
 }
 
@@ -1254,6 +1280,11 @@ int tsim_set_param_grad_groups(tsim_batch* b, int mask) {
   return 0;
 }
 int tsim_get_param_grad_groups(const tsim_batch* b) { return b ? b->pg_groups : -1; }
+int tsim_last_adjoint_launch(const tsim_batch* b, int32_t* out) {
+  if (!b || !out) return fail("last_adjoint_launch: null argument");
+  out[0] = b->adj_kernel; out[1] = b->adj_passes;
+  return 0;
+}
 
 int tsim_set_param_grad(tsim_batch* b, void* dL_dtables) {
   if (dL_dtables && pg_alloc(b)) return 1;

@@ -826,6 +826,15 @@ __global__ void TS_KLB_BWD k_backward_z(BwdArgs<R> a, R* zsave) {
   constexpr bool SAVEZ = true;
 #include "tsim_kernels_backward.h"
 }
+// ... and the SAVEZ twin of the CLOSED-LOOP adjoint kernel (k_backward's POLICY instantiations; tsim_push_closed_backward while a table-gradient
+// buffer is set): the same body once more, with the policy between the frames and the store of z.  A kernel of its own name, not
+// k_backward_z<..., POLICY = true, ...>: the set of k_forward / k_backward / k_backward_z / k_debug_eval instantiations is a fixed list
+// (tsim_launch.h ts_instantiated, tests/test_capi_symbols.py), and this one is counted beside it like k_forward_fr and k_frame_records.
+template <class R, int NRM, bool EXPJ, int LPE, class MS = void>
+__global__ void TS_KLB_BWD k_closed_backward_z(BwdArgs<R> a, R* zsave) {
+  constexpr bool POLICY = true, SAVEZ = true;
+#include "tsim_kernels_backward.h"
+}
 
 
 // ---- output_vjp for a statically known model with the fused evaluation (tsim_static_eval.h): the link sweep's states stay in registers, so

@@ -1,7 +1,7 @@
-// tsim_kernels_backward.h — the BODY of the adjoint kernel, included textually by k_backward and by its SAVEZ twin k_backward_z (tsim_kernels.h),
-// which differ only in `SAVEZ` (a constexpr bool) and `zsave`.  Textual inclusion rather than a shared device function: k_backward must stay the
+// tsim_kernels_backward.h — the BODY of the adjoint kernel, included textually by k_backward, by its SAVEZ twin k_backward_z and by the closed loop's
+// SAVEZ twin k_closed_backward_z (POLICY fixed to true) (tsim_kernels.h), which differ only in `SAVEZ` (a constexpr bool) and `zsave`.  Textual inclusion rather than a shared device function: k_backward must stay the
 // kernel it was, code bytes and registers (a body behind a function call boundary, even inlined, schedules differently; host/buildhash.py's
-// kernel table shows it).  Not a header of its own: it has no meaning outside those two function bodies.
+// kernel table shows it).  Not a header of its own: it has no meaning outside those function bodies.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   R* lds = reinterpret_cast<R*>(smem_raw);
   constexpr int NS = TS_WAVE / LPE;

@@ -1,6 +1,6 @@
 // tsim_launch.h — launch plans of the simulation kernels and the one launcher that runs them.
 //
-// A plan (TsPlan, made by tsim_hip.hip ts_plan and nowhere else) names one instantiation of k_forward, k_backward, k_backward_z, k_debug_eval,
+// A plan (TsPlan, made by tsim_hip.hip ts_plan and nowhere else) names one instantiation of k_forward, k_backward, k_backward_z, k_closed_backward_z, k_debug_eval,
 // k_frame_records, k_param_grad or k_param_grad_body and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
 // (tsim_hip.hip; the parameter passes: tsim_param_grad.hip, tsim_param_grad_body.hip), or a compiled-in model (tsim_static.h), whose translation units hold nothing but the
 // explicit instantiations of TsLaunch for their view: they are built with flags of their own (host/buildhash.py HIP_UNITS).
@@ -10,7 +10,8 @@
 #include "tsim_param_grad.h"
 #include "tsim_static_pusher.h"
 
-enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD, TS_K_PARAM_GRAD_BODY, TS_K_FRAME_RECORDS };
+enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD, TS_K_PARAM_GRAD_BODY, TS_K_FRAME_RECORDS,
+                TS_K_CLOSED_BACKWARD_Z };      // the closed-loop adjoint that saves z (k_closed_backward_z): POLICY launches only
 // the view of a launch: the generic kernels, a compiled-in model fully static, or its structure-static twin (parameters at run time)
 enum { TS_KM_GENERIC = 0, TS_KM_STATIC = 1, TS_KM_PARAM = 2 };
 using TsParamPusher = TsParam<TsStaticPusher>;
@@ -30,12 +31,13 @@ template <class MS> constexpr int ts_view_nrm() { return ts_static_nr<MS>() == 0
 
 // The instantiations there are, in one list: ts_plan runs the generic kernels where a compiled-in model has none, TsLaunch compiles exactly these
 // (tests/test_capi_symbols.py pins the set).  Every view: NRM 8 / 16 at 16 / 32 / 64 lanes per environment, a rotation-vector joint only at NRM 16
-// and 64 lanes; the closed loop: TactilePush's forward and adjoint (NRM 8).  A compiled-in model (ms_nrm != 0): its own NRM, no parameter pass;
+// and 64 lanes; the closed loop: TactilePush's forward and adjoint and the adjoint's SAVEZ twin k_closed_backward_z (NRM 8), the twin nowhere else.  A compiled-in model (ms_nrm != 0): its own NRM, no parameter pass;
 // fp64 not at 16 lanes (four environments' LDS is over the cap); the closed loop and the debug kernel at fp32 and 16 lanes only; the TsDefaultOpts<>
 // twin of the forward kernel at fp32 and 16 lanes, and there its k_forward_fr twin; k_frame_records wherever a FUSED compiled-in model has a forward kernel.
 constexpr bool ts_instantiated(int kernel, int ms_nrm, bool fp32, bool policy, bool default_opts, int nrm, bool expj, int lpe) {
   if ((expj && (nrm != 16 || lpe != 64)) || (nrm != 8 && nrm != 16) || (lpe != 16 && lpe != 32 && lpe != 64)) return false;
-  if (policy && (nrm != 8 || expj || (kernel != TS_K_FORWARD && kernel != TS_K_BACKWARD))) return false;
+  if (policy != (kernel == TS_K_CLOSED_BACKWARD_Z) && kernel != TS_K_FORWARD && kernel != TS_K_BACKWARD) return false;
+  if (policy && (nrm != 8 || expj)) return false;
   if (ms_nrm == 0) return !default_opts && kernel != TS_K_FRAME_RECORDS;
   if (kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || nrm != ms_nrm || expj) return false;
   if (default_opts) return kernel == TS_K_FORWARD && fp32 && lpe == 16;
@@ -66,7 +68,8 @@ template <class MS, bool POLICY, class R> struct TsLaunch {
   }
   static bool run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a);
   static bool run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a, int fpc);      // k_frame_records (TS_K_FRAME_RECORDS): fpc frames per block
-  static bool run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave = nullptr);      // zsave: k_backward_z (TS_K_BACKWARD_Z)
+  static bool run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave = nullptr);      // zsave: k_backward_z (TS_K_BACKWARD_Z), k_closed_backward_z
+  static bool run_closed_z(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave);      // TS_K_CLOSED_BACKWARD_Z; run() hands it over (a member of its own: the generic view's is instantiated in tsim_closed_backward_z.hip)
   static bool run(const TsPlan& p, hipStream_t st, const DbgArgs<R>& a);
   static bool run(const TsPlan& p, hipStream_t st, const PgArgs<R>& a);
   static bool run(const TsPlan& p, hipStream_t st, const PgBodyArgs<R>& a);
@@ -89,9 +92,13 @@ template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(cons
   else return false;
 }
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave) {
+  if (p.kernel == TS_K_CLOSED_BACKWARD_Z) return run_closed_z(p, st, a, zsave);
   if (p.kernel == TS_K_BACKWARD_Z)
     return shape<TS_K_BACKWARD_Z>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_backward_z<R, nrm, expj, lpe, POLICY, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a, zsave); });
   return shape<TS_K_BACKWARD>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_backward<R, nrm, expj, lpe, POLICY, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
+}
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run_closed_z(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave) {
+  return shape<TS_K_CLOSED_BACKWARD_Z>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_closed_backward_z<R, nrm, expj, lpe, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a, zsave); });
 }
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const DbgArgs<R>& a) {
   return shape<TS_K_DEBUG_EVAL>(p, [&](auto, auto, auto lpe) { hipLaunchKernelGGL((k_debug_eval<R, lpe, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
@@ -109,7 +116,8 @@ template <bool POLICY, class R, class A, class... Z> bool ts_launch(const TsPlan
   if (p.variant == TS_KM_PARAM) return TsLaunch<TsParamPusher, POLICY, R>::run(p, st, a, z...);
   return TsLaunch<void, POLICY, R>::run(p, st, a, z...);
 }
-// instantiated in their own units: tsim_static_pusher.hip, tsim_param_pusher.hip, their _policy twins, tsim_param_grad.hip, tsim_param_grad_body.hip
+// instantiated in their own units: tsim_static_pusher.hip, tsim_param_pusher.hip, their _policy twins, tsim_param_grad.hip, tsim_param_grad_body.hip,
+// tsim_closed_backward_z.hip
 extern template struct TsLaunch<TsStaticPusher, false, float>;
 extern template struct TsLaunch<TsStaticPusher, false, double>;
 extern template struct TsLaunch<TsStaticPusher, true, float>;
@@ -122,3 +130,6 @@ extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_
 extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PgArgs<double>&);
 extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const PgBodyArgs<float>&);
 extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PgBodyArgs<double>&);
+extern template bool TsLaunch<void, true, float>::run_closed_z(const TsPlan&, hipStream_t, const BwdArgs<float>&, float*);
+extern template bool TsLaunch<void, true, double>::run_closed_z(const TsPlan&, hipStream_t, const BwdArgs<double>&, double*);
+void ts_closed_slots_launch(int32_t* slots, int nframes, hipStream_t st);      // tsim_closed_backward_z.hip: slots[f] = f, the last frame -1

@@ -23,6 +23,11 @@ OBS_MODES = {"tactile_flatten": (0, 393), "no_tactile": (1, 3), "privilege": (2,
 
 
 class FusedPushEpisode:
+    """One TactilePush episode with the policy inside the launches: rollout() / backward(), evaluate(), collect().
+
+    Table gradient: while `env.sim.set_param_grad(buf)` is set, backward() also adds the episode's per-environment dLoss/d(parameter) into `buf`
+    for the groups `env.sim.set_param_grad_groups` enabled.  `buf` ACCUMULATES across episodes until the caller zeroes it."""
+
     def __init__(self, env, actor, horizon):
         """env: BatchedTactilePushEnv (its BatchSim, dtype, device, observation_type: tactile_flatten / no_tactile / privilege — the
         three GD configurations of examples/TactilePushExp/cfg); actor: algorithms.batched_gd.Actor (obs -> 64 -> 64 -> 3)."""
@@ -142,16 +147,24 @@ class FusedPushEpisode:
         self.loss = -rew.sum()
         return self.loss
 
-    def backward(self):
+    def backward(self, df_du=None):
         """Adjoint launch of the episode rollout() ran, then the weight gradients: sets .grad of the actor's weights and biases
-        (assigned, not accumulated; un-normalised, as rollout_loss(...).backward() would)."""
+        (assigned, not accumulated; un-normalised, as rollout_loss(...).backward() would).  df_du: an optional [T, B, 6] tensor that receives
+        the gradient w.r.t. the applied actions [tanh(policy), disturbance, 0] of every frame.
+
+        Parameter gradient: with `sim.set_param_grad(buf)` set (groups: `sim.set_param_grad_groups`, as on the open-loop path) the same launch
+        sequence also leaves the episode's per-environment table gradient dLoss/d(table entry) in `buf` [B, table_size].  It ADDS: `buf`
+        accumulates across episodes until the caller zeroes it, and only the enabled groups' columns are touched.  tac0 and the first
+        observation are inputs: their dependence on the parameters is not propagated (include/tsim_env.h tsim_push_closed_backward)."""
         sim = self.sim
         if not getattr(self, "_recorded", False):
             raise RuntimeError("FusedPushEpisode.backward: the last roll-out was not recorded (evaluate())")
+        if df_du is not None and (df_du.dtype != self.dt or df_du.device != self.dev or tuple(df_du.shape) != (self.T, self.B, 6) or not df_du.is_contiguous()):
+            raise ValueError("FusedPushEpisode.backward: df_du must be a contiguous [%d, %d, 6] %s tensor on %s" % (self.T, self.B, self.dt, self.dev))
         st = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
         capi.check(capi.lib().tsim_push_closed_backward(sim._h, C.byref(self._pol), _p(self.goal), self.T, self.env.frame_skip,
                                                         _p(self.df_dq), _p(self.df_dvar), _p(self.du_direct), _p(self.u), _p(self.h1), _p(self.h2),
-                                                        _p(self.g1), _p(self.g2), _p(self.g3), _p(self.dobs_tac), None, st))
+                                                        _p(self.g1), _p(self.g2), _p(self.g3), _p(self.dobs_tac), _p(df_du), st))
         l1, l2, l3 = self.lin
         g1, g2, g3 = self.g1, self.g2, self.g3
         T = self.T

@@ -121,6 +121,17 @@ class BatchSim:
         mask = capi.lib().tsim_get_param_grad_groups(self._h)
         return tuple(g for g, bit in self.PARAM_GRAD_GROUPS.items() if mask & bit)
 
+    ADJOINT_KERNELS = ("k_backward", "k_backward_z", "k_closed_backward_z")      # include/tsim.h TSIM_ADJ_*
+
+    def last_adjoint_launch(self):
+        """What the most recent adjoint launch of this batch ran (include/tsim.h tsim_last_adjoint_launch): {"kernel": "k_backward", its twin
+        "k_backward_z" that also saves z (a table-gradient buffer was set), or the closed-loop adjoint's twin "k_closed_backward_z" (None: no adjoint
+        launch yet); "param_passes": the passes launched behind it, a tuple out of "k_param_grad", "k_param_grad_body"}."""
+        out = (C.c_int32 * 2)()
+        capi.check(capi.lib().tsim_last_adjoint_launch(self._h, out))
+        return {"kernel": self.ADJOINT_KERNELS[out[0]] if out[0] >= 0 else None,
+                "param_passes": tuple(k for i, k in enumerate(("k_param_grad", "k_param_grad_body")) if out[1] >> i & 1)}
+
     def reset(self, q0, qd0=None, backward_flag=False):
         q0 = self._chk(q0, self.ndof_r, "q0")
         qd0 = self._chk(qd0, self.ndof_r, "qd0")

@@ -66,6 +66,7 @@ HIP_UNITS = [("tsim_hip.hip", []), ("tsim_static_pusher.hip", ["-ffinite-math-on
              ("tsim_param_pusher_policy.hip", ["-ffinite-math-only", "-fno-signed-zeros"]),       # ... of the structure-static kernels (round 6: closed loop with per-environment tables)
              ("tsim_param_grad.hip", []),                                                         # the parameter-gradient pass (tsim_set_param_grad): generic flags
              ("tsim_param_grad_body.hip", []),                                                    # its body groups (tsim_set_param_grad_groups): a unit of their own, so that k_param_grad's code does not move
+             ("tsim_closed_backward_z.hip", []),                                                  # the generic closed-loop adjoint kernels that save z (tsim_push_closed_backward with a table-gradient buffer): a unit of their own, so that tsim_hip.hip's kernels do not move
              ("tsim_model.cpp", ["-ffp-contract=off"])]                                           # host only: the model loader (include/tsim_model.h); plain double arithmetic, no contraction
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC"]      # units that are not .hip: no device code
 
@@ -141,7 +142,7 @@ def write_kernel_table(lib=None, out=None):
 
 
 def kernel_name(kernel, dtype, nr, has_exp, lanes, variant, policy=False, default_opts=False):
-    """Mangled name of the instantiation of k_forward / k_backward / k_frame_records / k_forward_fr a batch launches (csrc/tsim_hip.hip ts_plan) and a readable form of it.
+    """Mangled name of the instantiation of k_forward / k_backward / k_closed_backward_z / k_frame_records / k_forward_fr a batch launches (csrc/tsim_hip.hip ts_plan) and a readable form of it.
     default_opts: every solver / scheduling option of the batch is at its default (tsim_get_option TSIM_OPT_ALL_DEFAULT): the fp32 forward launch of a
     compiled-in model at 16 lanes per environment then runs the TsDefaultOpts<> instantiation (csrc/tsim_static.h)."""
     nrm, expj, lpe = (16, True, 64) if has_exp else ((8 if nr <= 8 else 16), False, lanes)
@@ -158,6 +159,12 @@ def kernel_name(kernel, dtype, nr, has_exp, lanes, variant, policy=False, defaul
         return ("_Z15k_frame_recordsI%sLi%dE%sEv7FwdArgsIT_Ei" % (r[0], lpe, ms[0]), "k_frame_records<%s, LPE=%d, %s>" % (r[1], lpe, ms[1]))
     if kernel == "k_forward_fr":
         return ("_Z12k_forward_frI%sLi%dELi%dE%sEv7FwdArgsIT_E" % (r[0], nrm, lpe, ms[0]), "k_forward_fr<%s, NRM=%d, LPE=%d, %s>" % (r[1], nrm, lpe, ms[1]))
+    # the closed-loop adjoint that also saves z (csrc/tsim_kernels.h k_closed_backward_z; FusedPushEpisode.backward with a table-gradient buffer set): no
+    # POLICY parameter, it is the closed loop's; wherever a closed-loop k_backward is (generic: every shape; a compiled-in model: fp32, 16 lanes)
+    if kernel == "k_closed_backward_z":
+        back = {"generic": 1, "static:pusher": 2, "param:pusher": 4}[variant]      # the view's class names are substitution candidates in front of T_
+        return ("_Z19k_closed_backward_zI%sLi%dELb%dELi%dE%sEv7BwdArgsIT_EPS%d_" % (r[0], nrm, int(expj), lpe, ms[0], back),
+                "k_closed_backward_z<%s, NRM=%d, EXPJ=%s, LPE=%d, %s>" % (r[1], nrm, str(expj).lower(), lpe, ms[1]))
     args = {"k_forward": "7FwdArgs", "k_backward": "7BwdArgs"}[kernel]
     mangled = "_Z%d%sI%sLi%dELb%dELi%dELb%dE%sEv%sIT_E" % (len(kernel), kernel, r[0], nrm, int(expj), lpe, int(policy), ms[0], args)
     return mangled, "%s<%s, NRM=%d, EXPJ=%s, LPE=%d, POLICY=%s, %s>" % (kernel, r[1], nrm, str(expj).lower(), lpe, str(policy).lower(), ms[1])

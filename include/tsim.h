@@ -123,7 +123,12 @@ int tsim_step(tsim_batch* b, const void* u, int num_steps, void* q_out, void* qd
  * right after reset (envs/tactile_push_env.py:157) or after forward() where the pad is too large to be read out inside the step
  * (examples/RollingBallExp/test_sim_speed.py:77-80: 40 000 taxels).  tsim_readout is two launches — kinematics of the current state,
  * then one kernel whose lanes are taxels — or, for pads of >= 4096 taxels right after a forward launch, the second one alone: that
- * launch leaves the pose records of the state it ends in.  Same results either way; any other change of state (reset, masked reset,
+ * launch leaves the pose records of the state it ends in.  Same results either way, and the same bits as the tactile frames tsim_step /
+ * tsim_rollout write — to round-off where a sensor has more than four primitives and the launch reads out inside the stepping kernel
+ * (closed-loop launches, launches under capture, TSIM_INKERNEL_READOUT=1, more than 64 (sensor, primitive) combinations or 16 sensors):
+ * that read-out stages a sensor's primitives in groups of four and adds the taxel's projected outputs group by group, where the taxel
+ * kernels add the forces and project once (measured 5e-8 of the frame's maximum in fp32, 1e-16 in fp64, on a taxel that two groups load:
+ * tests/test_gpu_tactile_readout_shapes.py).  Any other change of state (reset, masked reset,
  * new model tables, cache pop) and any HIP-graph capture of this batch's launches switch back to two. */
 int tsim_get_state(tsim_batch* b, void* q_out, void* qd_out, void* stream);
 int tsim_readout(tsim_batch* b, void* var_out, void* tac_out, void* stream);

@@ -105,11 +105,16 @@ def test_non_finite_action_is_confined_to_its_environment(pusher_model):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
-@pytest.mark.parametrize("name", ["pusher", "dclaw_position_control", "tactile_insertion", "stable_grasp", "tactile_pad"])
+@pytest.mark.parametrize("name", ["pusher", "dclaw_position_control", "tactile_insertion", "stable_grasp", "tactile_pad",
+                                  "dclaw_position_control:touching", "stable_grasp:grasped"])
 def test_on_demand_readout_equals_the_step_outputs(name, dtype):
     """tsim_readout (k_readout + k_taxels: its own kernels, an fp32 far-test in front of the double-precision taxel position, per-block
     staging of the (sensor, primitive) records — 22 of them for stable_grasp) returns bit for bit what the stepping kernel wrote for the
-    same state, on every reference model."""
+    same state, on every reference model (the launches here defer their tactile frames to the taxel kernels; against the IN-KERNEL read-out the
+    statement holds to round-off where a sensor has more than four primitives: include/tsim.h, tests/test_gpu_tactile_readout_shapes.py).  The scenarios of D'Claw and stable_grasp end with no taxel loaded (zeros and the variables are
+    compared); each has a second one in which taxels carry a force: the claw two env-steps into its grasp, the fingertips still on the
+    cap, and the gripper held closed on the bar at grasp height (all 260 taxels of both pads)."""
+    name, _, scenario = name.partition(":")
     import os
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -120,7 +125,7 @@ def test_on_demand_readout_equals_the_step_outputs(name, dtype):
     B, T = 5, 6
     if name in ("dclaw_position_control", "tactile_insertion"):
         from test_gpu_models import _inputs
-        T = 12                                                       # the grasps close within ~10 env-steps
+        T = 2 if scenario == "touching" else 12                      # the grasps close within ~10 env-steps; the claw's taxels are loaded in the first three
         q0, u = _inputs(name, m, B, T)
     elif name == "pusher":
         T = 40
@@ -128,6 +133,10 @@ def test_on_demand_readout_equals_the_step_outputs(name, dtype):
         u[:, :, 0] = 0.9                                             # drive the pad into the box
     elif name == "tactile_pad":
         q0 = np.zeros((B, m.ndof_r)); u = np.tile(np.array([0.0, 0.0, 0.2]), (B, T, 1)); T = 6
+    elif scenario == "grasped":                                      # stable_grasp at grasp height, the finger targets inside the bar (envs/stable_grasp.py GRASP_HEIGHT, FINGER)
+        from tactilesimulation_amd.envs.stable_grasp import FINGER, GRASP_HEIGHT
+        q0 = np.zeros((B, m.ndof_r)); q0[:, 1] = 0.004 * np.arange(B); q0[:, 2] = GRASP_HEIGHT; q0[:, 4:6] = FINGER
+        u = np.tile(q0[:, None, :6], (1, T, 1))
     else:                                                            # stable_grasp: close the fingers on the stack
         q0 = np.zeros((B, m.ndof_r)); u = np.zeros((B, T, m.ndof_u)); u[:, :, -2:] = 1.0
     sim = BatchSim(m, B, dtype=dtype, tape_capacity=0)
@@ -148,8 +157,10 @@ def test_on_demand_readout_equals_the_step_outputs(name, dtype):
         else:
             assert float((tac - o["tactile"]).abs().max()) <= 1e-5 * float(tac.abs().max())
             assert float((var - o["var"]).abs().max()) <= 1e-6
-    if name in ("pusher", "tactile_pad", "tactile_insertion"):       # scenarios known to load taxels (the other two compare zeros and variables)
+    if name in ("pusher", "tactile_pad", "tactile_insertion") or scenario:      # scenarios that load taxels (the first ones of D'Claw and stable_grasp compare zeros and variables)
         assert float(tac.abs().max()) > 0, "the scenario never loaded a taxel: nothing was compared"
+    if scenario:
+        assert int((tac.reshape(B, -1, 3) != 0).any(-1).sum(1).min()) >= (260 if scenario == "grasped" else 4)      # in every environment
 
 
 @pytest.mark.parametrize("name,static", [("pusher", True), ("pusher", False), ("dclaw_position_control", False), ("tactile_insertion", False)])

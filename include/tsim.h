@@ -168,6 +168,42 @@ int tsim_rollout(tsim_batch* b, const void* u, int num_frames, int num_steps, co
 int tsim_backward_episode(tsim_batch* b, int num_frames, int num_steps, const int32_t* tactile_slot,
                           const void* df_dq, const void* df_dvar, const void* df_dtac, void* df_du, void* stream);
 
+/* Forward-mode tangent pass (no reference counterpart): the derivative of the outputs of the newest num_frames * num_steps taped sub-steps along
+ * ndir directions at once (1 .. TSIM_TANGENT_MAX_DIR) — J v where tsim_backward_episode + tsim_get_adjoint + tsim_set_param_grad give J^T w.
+ * It reads the tape and writes the caller's buffers, nothing else: the tape is not popped, the state, the carried adjoint, the cache and the pose
+ * records are not touched; it may be called any number of times between a recorded roll-out and its adjoint, which afterwards returns the bits it
+ * would have returned without the calls.  No host synchronisation, no allocation.
+ * Inputs (device memory, the batch's real type; NULL = zeros), direction outermost:
+ *   du [ndir][num_frames][B][ndof_u];  dq0, dqd0 [ndir][B][ndof_r]: the tangent of the state at the window's start;
+ *   dtables [ndir][B][tsim_table_size]: ONLY the TSIM_PG_CONTACT columns are read (contact pair and sensor kn kt mu damping, dof damping);
+ *   every other entry is not read at all.
+ * Outputs (NULL = not written), time-major like tsim_rollout's with the direction outermost:
+ *   dq_out, dqd_out [ndir][num_frames][B][ndof_r];  dvar_out [ndir][num_frames][B][ndof_var];
+ *   dtac_out [ndir][num_masked][B][ndof_tactile] (tactile_slot as in tsim_rollout).
+ * Per BDF1 sub-step, with H the taped Newton matrix of the accepted iterate, K = dg/dq at it, M the mass matrix, D du the motor term
+ * (dtu / ca on the motor's dof; a clipped force control has none) and g = r / ca:
+ *     s = -K dq0 + h M dqd0 + D du - (dg/dp) dp ,   H y = s ,   dq1 = dq0 + y ,   dqd1 = cv y
+ * — the exact transpose of the adjoint launches (rhs = lam_q + cv lam_v; H^T z = rhs; lam_q' = lam_q - K^T z; lam_v' = h M z; dL/du = D^T z;
+ * dL/dp = -(dg/dp)^T z), so a sub-step that did not converge is treated as the adjoint treats it, and the stick / slip switch and the joint
+ * limits give the one-sided derivative of the piece each point is on.  BDF2 sub-steps (tape record >= 2) carry the tangents of the two states
+ * before them: kv = -4/3 dq0 + 1/3 dq_1, mv = 8h/9 dqd0 - 2h/9 dqd_1, s = K kv + M mv + ..., dq1 = y - kv.  At a frame's end dq, dqd are
+ * written, dvar = J_var dq, and every loaded taxel emits A^T R_PA^T (Jx dx + Jv dxd - dth x F + dF/dp_sensor dp); an unloaded taxel an exact 0.
+ * Parameters are the environment's row of tsim_set_env_tables, or the shared model's.  Directions are independent: a direction's bits do
+ * not depend on ndir or on the other directions.
+ * Returns non-zero (tsim_last_error) and launches nothing for: a null batch; ndir outside 1 .. 8; no tape recorded or a window longer than the
+ * tape; a BDF2 model whose window does not start at tape record 0 (no tangent is carried across calls).
+ * Out of scope: the body-group columns (TSIM_PG_INERTIAL / MOTOR / LIMIT), geometry and the float header as directions; the fused closed
+ * loop (tsim_env.h); the B = 1 shim; torch forward-mode AD. */
+enum { TSIM_TANGENT_MAX_DIR = 8 };
+int tsim_tangent_episode(tsim_batch* b, int num_frames, int num_steps, int ndir, const int32_t* tactile_slot,
+                         const void* du, const void* dq0, const void* dqd0, const void* dtables,
+                         void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, void* stream);
+/* Diagnostics: the static launch geometry of a tsim_tangent_episode call of ndir directions (with_dtables: dtables given), as tsim_launch_info
+ * reports the forward / backward kernels': out[0] = LDS bytes per block (the contexts and the launch's tangent blocks), out[1] = threads per
+ * block, out[2] = blocks, out[3] = lanes per environment.  The lanes are the batch's (tsim_launch_info), doubled until a block holds the tangent
+ * state of TSIM_TANGENT_MAX_DIR directions with parameters, so they do not depend on ndir or with_dtables; the LDS bytes do. out = int32[4]. */
+int tsim_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, int32_t* out);
+
 /* sim.backward() results df_dq0 / df_dqdot0                    envs/redmax_torch_functions.py:92-100
  * = the carried adjoint once the whole tape has been popped. [B][ndof_r] each. */
 int tsim_get_adjoint(tsim_batch* b, void* df_dq0, void* df_dqd0, void* stream);

@@ -778,6 +778,7 @@ static void decide_stage_cpt(tsim_batch* b) {
 // kernel: TS_K_*; policy: the closed loop; lpe: lanes per environment asked for by this launch (0: the batch's, TSIM_LPE /
 // tsim_set_lanes_per_env); the precision is the batch's.  The view is the batch's (kernel_mode) — for the adjoint kernels only on a tape whose
 // K the forward wrote (tape_k_ok: the fused adjoint reads it) — where it has an instantiation (ts_instantiated), else the generic kernels.
+enum { TS_TAN_LDS_CAP = 64 * 1024 };      // dynamic LDS of a k_tangent block
 static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   int forced = lpe ? lpe : b->lpe_forced;
   if (kernel == TS_K_DEBUG_EVAL && !forced) forced = TS_WAVE;      // the debug kernel: one environment per wavefront unless a shape is forced
@@ -786,10 +787,21 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
   const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z || kernel == TS_K_CLOSED_BACKWARD_Z;
-  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
   p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
+  if (kernel == TS_K_TANGENT) {
+    // the tangent pass: every slot holds its tangent block behind the contexts (tsim_tangent.h).  The lanes are chosen for TSIM_TANGENT_MAX_DIR
+    // directions with parameters, whatever the launch asks for — the shape must not depend on ndir or on which inputs are given —: where the
+    // block's LDS does not hold that, fewer environments share a wavefront.  grid and lds are those of the contexts; launch_tangent adds the
+    // launch's own tangent blocks
+    const size_t most = (size_t)ts_tan_slot_reals(b->nr, b->nu, ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr), 4, TS_TAN_MAX_DIR) * b->esz;
+    while (p.lpe < TS_WAVE && lds_bytes_for(b, TS_WAVE / p.lpe) + (TS_WAVE / p.lpe) * most > TS_TAN_LDS_CAP) p.lpe *= 2;
+    const int ns = TS_WAVE / p.lpe;
+    p.grid = (unsigned)((b->B + ns - 1) / ns);
+    p.lds = lds_bytes_for(b, ns);
+  }
   return p;
 }
 // the kernel arguments that come from the batch; each launch sets its own
@@ -1013,6 +1025,35 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
   return launch_param_passes<R>(b, n, seed_stride, frames, tac_slot, df_dtac, st);
 }
 
+// The tangent pass over the newest T x S taped sub-steps (tsim_tangent_episode): one launch of the generic k_tangent, whatever the batch's view (a
+// compiled-in model's tape has K in its records: a.tk), on the batch's per-environment rows.  Reads the tape, writes the caller's buffers.
+// the plan of a tangent launch of ndir directions: ts_plan's shape, its LDS grown by the launch's own tangent blocks (ctx_lds: the contexts' part,
+// where the blocks begin).  launch_tangent and tsim_tangent_launch_info both take it from here
+static TsPlan tangent_plan(const tsim_batch* b, int ndir, bool with_dtab, size_t* ctx_lds) {
+  TsPlan plan = ts_plan(b, TS_K_TANGENT, false, 0);
+  *ctx_lds = plan.lds;
+  const int nhist = b->I[TSIM_IH_INTEGRATOR] == 2 ? 4 : 2, P = with_dtab ? ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr) : 0;
+  plan.lds += (((size_t)(TS_WAVE / plan.lpe) * ts_tan_slot_reals(b->nr, b->nu, P, nhist, ndir) * b->esz + 15) / 16) * 16;
+  return plan;
+}
+template <class R>
+static int launch_tangent(tsim_batch* b, int T, int S, int ndir, const int32_t* tac_slot, const void* du, const void* dq0, const void* dqd0, const void* dtab,
+                          void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, hipStream_t st) {
+  TanArgs<R> a{};
+  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec;
+  a.B = b->B; a.n = T * S; a.t_end = b->t_cur; a.nsub = S; a.nframes = T; a.ndir = ndir; a.tk = b->tape_k;
+  a.stage_cpt = b->stage_cpt; a.cull = b->pair_cull; a.tac_slot = tac_slot; a.tape = (const R*)b->tape;
+  a.du = (const R*)du; a.dq0 = (const R*)dq0; a.dqd0 = (const R*)dqd0; a.dtab = (const R*)dtab;
+  a.dq_out = (R*)dq_out; a.dqd_out = (R*)dqd_out; a.dvar_out = (R*)dvar_out; a.dtac_out = (R*)dtac_out;
+  size_t ctx_lds;
+  const TsPlan plan = tangent_plan(b, ndir, dtab != nullptr, &ctx_lds);
+  a.xoff = (int)(ctx_lds / b->esz);
+  if (plan.lds > TS_TAN_LDS_CAP) return fail("tangent_episode: the tangent state of " + std::to_string(ndir) + " directions does not fit the block's LDS for this model");
+  if (!TsLaunch<void, false, R>::run(plan, st, a)) return fail("no k_tangent instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 const char* tsim_last_error(void) { return g_err.c_str(); }
@@ -1109,6 +1150,14 @@ int tsim_tape_len(const tsim_batch* b) { return b->record ? b->t_cur : 0; }
 int tsim_launch_info(const tsim_batch* b, int32_t* out) {
   const LaunchShape L = launch_shape(b, b->lpe_forced);
   out[0] = (int32_t)L.lds; out[1] = TS_WAVE; out[2] = (int32_t)L.grid; out[3] = L.lpe;
+  return 0;
+}
+int tsim_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, int32_t* out) {
+  if (!b || !out) return fail("tangent_launch_info: null argument");
+  if (ndir < 1 || ndir > TSIM_TANGENT_MAX_DIR) return fail("tangent_launch_info: ndir must be 1 .. " + std::to_string((int)TSIM_TANGENT_MAX_DIR));
+  size_t ctx_lds;
+  const TsPlan p = tangent_plan(b, ndir, with_dtables != 0, &ctx_lds);
+  out[0] = (int32_t)p.lds; out[1] = TS_WAVE; out[2] = (int32_t)p.grid; out[3] = p.lpe;
   return 0;
 }
 int tsim_kernel_timing(tsim_batch* b, int enable) { b->kt_on = enable ? 1 : 0; return 0; }
@@ -1411,6 +1460,21 @@ int tsim_backward_episode(tsim_batch* b, int num_frames, int num_steps, const in
   b->t_cur -= (int)n;
   pose_invalidate(b, (hipStream_t)stream);
   return 0;
+}
+
+int tsim_tangent_episode(tsim_batch* b, int num_frames, int num_steps, int ndir, const int32_t* tactile_slot, const void* du, const void* dq0, const void* dqd0,
+                         const void* dtables, void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, void* stream) {
+  if (!b) return fail("tangent_episode: null batch");
+  if (ndir < 1 || ndir > TSIM_TANGENT_MAX_DIR) return fail("tangent_episode: ndir must be 1 .. " + std::to_string((int)TSIM_TANGENT_MAX_DIR) + ", got " + std::to_string(ndir));
+  if (!b->record || b->t_cur <= 0) return fail("tangent_episode: no tape recorded (reset(backward_flag=True), then a roll-out)");
+  if (num_frames <= 0 || num_steps <= 0) return fail("tangent_episode: num_frames and num_steps must be positive");
+  const long long n = (long long)num_frames * num_steps;
+  if (n > b->t_cur) return fail("tangent_episode: only " + std::to_string(b->t_cur) + " sub-steps on the tape");
+  if (b->I[TSIM_IH_INTEGRATOR] == 2 && n != b->t_cur)
+    return fail("tangent_episode: a BDF2 model's window must start at tape record 0 (no tangent is carried across calls); the tape holds " + std::to_string(b->t_cur) + " sub-steps");
+  TS_DEVICE(b);
+  return b->dtype == TSIM_F32 ? launch_tangent<float>(b, num_frames, num_steps, ndir, tactile_slot, du, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, (hipStream_t)stream)
+                              : launch_tangent<double>(b, num_frames, num_steps, ndir, tactile_slot, du, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, (hipStream_t)stream);
 }
 
 int tsim_get_adjoint(tsim_batch* b, void* df_dq0, void* df_dqd0, void* stream) {

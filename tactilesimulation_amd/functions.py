@@ -242,3 +242,34 @@ class BatchedEpisodicParamSimFunction(autograd.Function):
         g = (lq.to(ctx.in_dtype) if ctx.need[0] else None, lv.to(ctx.in_dtype) if ctx.need[1] else None,
              du.to(ctx.in_dtype) if ctx.need[2] else None, gtab.to(ctx.tab_dtype) if gtab is not None else None)
         return g + (None, None, None, None)
+
+
+def episode_jacobian(sim, num_frames, num_steps, columns, tactile_mask=None, outputs=("q", "var", "tactile")):
+    """Jacobian of the frames' outputs of the recorded episode w.r.t. table columns, per environment — the forward-mode companion of
+    BatchedEpisodicParamSimFunction's table gradient (which gives one row J^T w per backward pass; this gives J column by column).
+
+    sim holds the tape of the newest num_frames x num_steps sub-steps (reset(backward_flag=True) + rollout, e.g. the forward of
+    BatchedEpisodicParamSimFunction with grad_mode); columns: entries of sim.model.param_columns() — (kind, name, field, column) — or plain
+    column indices, all among the contact columns (BatchSim.tangent_episode reads no other).  One unit direction per column, eight per launch
+    (include/tsim.h tsim_tangent_episode); the tape, the state and the carried adjoint are left as they are, so the episode's backward pass may
+    follow.  Returns [B, n_out, len(columns)] with n_out the outputs named in `outputs`, each flattened frame-major ([T, dim], tactile:
+    [n_masked, dim]) and concatenated in the order q, var, tactile."""
+    cols = [int(c[3]) if isinstance(c, (tuple, list)) else int(c) for c in columns]
+    allowed = {int(c) for (_, _, _, c) in sim.model.param_columns()}
+    bad = [c for c in cols if c not in allowed]
+    if bad:
+        raise ValueError("episode_jacobian: columns %s are not among model.param_columns()" % bad)
+    ntab = sim.base_tables().shape[1]
+    keys = [k for k in ("q", "var", "tactile") if k in outputs and (k == "q" or getattr(sim, "ndof_" + k))]
+    blocks = []
+    for c0 in range(0, len(cols), sim.TANGENT_MAX_DIR):
+        chunk = cols[c0:c0 + sim.TANGENT_MAX_DIR]
+        dt = torch.zeros((len(chunk), sim.B, ntab), device=sim.device, dtype=sim.dtype)
+        for d, c in enumerate(chunk):
+            dt[d, :, c] = 1.0
+        o = sim.tangent_episode(num_frames, num_steps, dtables=dt, tactile_mask=tactile_mask, want_var="var" in keys, want_tactile="tactile" in keys)
+        # [ndir, n, B, dim] -> [B, n * dim, ndir]
+        blocks.append(torch.cat([o["d" + k].permute(2, 1, 3, 0).reshape(sim.B, -1, len(chunk)) for k in keys], 1))
+    if not blocks:
+        return torch.zeros((sim.B, 0, 0), device=sim.device, dtype=sim.dtype)
+    return torch.cat(blocks, 2)

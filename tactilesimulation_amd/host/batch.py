@@ -217,6 +217,48 @@ class BatchSim:
                                                     self._stream()))
         return du
 
+    TANGENT_MAX_DIR = 8      # include/tsim.h TSIM_TANGENT_MAX_DIR
+
+    def tangent_episode(self, num_frames, num_steps, du=None, dq0=None, dqd0=None, dtables=None, tactile_mask=None, want_qd=False, want_var=True,
+                        want_tactile=True):
+        """Forward-mode tangent of the newest num_frames env-steps (num_steps sub-steps each) in one launch (include/tsim.h tsim_tangent_episode):
+        J v where backward_episode + get_adjoint + set_param_grad give J^T w.  Directions, leading dimension ndir (1 .. 8, taken from the inputs
+        given, which must agree; all None: one zero direction): du [ndir, T, B, ndof_u], dq0 / dqd0 [ndir, B, ndof_r] (the tangent of the state
+        at the window's start), dtables [ndir, B, table_size] (only the columns of model.param_columns() are read).  Returns a dict dq [ndir, T, B,
+        ndof_r], dqd (want_qd), dvar [ndir, T, B, ndof_var], dtactile [ndir, n_masked, B, ndof_tactile].  The tape, the state and the carried adjoint
+        are left as they are."""
+        T = int(num_frames)
+        slots, nm = self._tactile_slots(T, tactile_mask)
+        ntab = capi.lib().tsim_table_size(self._h)
+        ndir = None
+        ins = []
+        for t, tail, name in ((du, (T, self.B, self.ndof_u), "du"), (dq0, (self.B, self.ndof_r), "dq0"), (dqd0, (self.B, self.ndof_r), "dqd0"),
+                              (dtables, (self.B, ntab), "dtables")):
+            if t is None:
+                ins.append(None)
+                continue
+            t = t.to(device=self.device, dtype=self.dtype).contiguous()
+            if t.dim() != len(tail) + 1 or tuple(t.shape[1:]) != tail:
+                raise ValueError("%s: expected [ndir, %s], got %s" % (name, ", ".join(str(x) for x in tail), tuple(t.shape)))
+            if ndir is not None and t.shape[0] != ndir:
+                raise ValueError("%s: %d directions, the other inputs have %d" % (name, t.shape[0], ndir))
+            ndir = int(t.shape[0])
+            ins.append(t if t.numel() else None)
+        ndir = 1 if ndir is None else ndir
+        if not 1 <= ndir <= self.TANGENT_MAX_DIR:
+            raise ValueError("tangent_episode: 1 .. %d directions per launch, got %d" % (self.TANGENT_MAX_DIR, ndir))
+        new = lambda n, d: torch.empty((ndir, n, self.B, d), device=self.device, dtype=self.dtype)
+        o = {"dq": new(T, self.ndof_r)}
+        if want_qd:
+            o["dqd"] = new(T, self.ndof_r)
+        if want_var and self.ndof_var:
+            o["dvar"] = new(T, self.ndof_var)
+        if want_tactile and self.ndof_tactile:
+            o["dtactile"] = new(nm, self.ndof_tactile)
+        capi.check(capi.lib().tsim_tangent_episode(self._h, T, int(num_steps), ndir, _ptr(slots), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(ins[3]),
+                                                   _ptr(o["dq"]), _ptr(o.get("dqd")), _ptr(o.get("dvar")), _ptr(o.get("dtactile")), self._stream()))
+        return o
+
     def get_state(self):
         q, qd = self.empty(self.ndof_r), self.empty(self.ndof_r)
         capi.check(capi.lib().tsim_get_state(self._h, _ptr(q), _ptr(qd), self._stream()))
@@ -347,4 +389,11 @@ class BatchSim:
     def launch_info(self):
         out = (C.c_int32 * 4)()
         capi.lib().tsim_launch_info(self._h, out)
+        return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}
+
+    def tangent_launch_info(self, ndir=8, with_dtables=True):
+        """launch_info() of a tangent_episode call of ndir directions (include/tsim.h tsim_tangent_launch_info): its lanes per environment may be
+        wider than the batch's, where a block would not hold the tangent state of eight directions"""
+        out = (C.c_int32 * 4)()
+        capi.check(capi.lib().tsim_tangent_launch_info(self._h, int(ndir), int(bool(with_dtables)), out))
         return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}

@@ -172,11 +172,20 @@ int tsim_backward_episode(tsim_batch* b, int num_frames, int num_steps, const in
  * ndir directions at once (1 .. TSIM_TANGENT_MAX_DIR) — J v where tsim_backward_episode + tsim_get_adjoint + tsim_set_param_grad give J^T w.
  * It reads the tape and writes the caller's buffers, nothing else: the tape is not popped, the state, the carried adjoint, the cache and the pose
  * records are not touched; it may be called any number of times between a recorded roll-out and its adjoint, which afterwards returns the bits it
- * would have returned without the calls.  No host synchronisation, no allocation.
+ * would have returned without the calls.  No host synchronisation and no allocation, with one exception: with a body group on and dtables
+ * given, the body columns' part of the sources is computed into a workspace of the batch, [ndir][num_frames * num_steps][B][ndof_r] reals, which
+ * grows only.  The first call that needs it, or needs it larger, allocates it and synchronises the stream; later calls of the same or a smaller
+ * size do neither.  A call that would have to allocate under stream capture is refused: capture a launch only after a warm-up call of that
+ * size.  A workspace that a captured graph names is kept until the batch is destroyed, so a replay after a later, larger call stays valid.  The
+ * workspace is freed with the batch; nothing is allocated while no body group is on.  Because it belongs to the batch, tangent calls of one batch
+ * that read body columns must be issued on one stream, or be ordered by the caller: two of them in flight at once would share it.
  * Inputs (device memory, the batch's real type; NULL = zeros), direction outermost:
  *   du [ndir][num_frames][B][ndof_u];  dq0, dqd0 [ndir][B][ndof_r]: the tangent of the state at the window's start;
- *   dtables [ndir][B][tsim_table_size]: ONLY the TSIM_PG_CONTACT columns are read (contact pair and sensor kn kt mu damping, dof damping);
- *   every other entry is not read at all.
+ *   dtables [ndir][B][tsim_table_size]: the TSIM_PG_CONTACT columns are always read (contact pair and sensor kn kt mu damping, dof damping),
+ *   and with them the columns of every body group that is on in the batch's tsim_set_param_grad_groups mask — TSIM_PG_INERTIAL: link mass,
+ *   centre of mass, inertia; TSIM_PG_MOTOR: motor lo hi P D; TSIM_PG_LIMIT: dof limit lo hi k (the TSIM_TAB_LINK / MOTOR / LIMIT columns).
+ *   Every other entry is not read at all.  With the default mask (TSIM_PG_CONTACT) a body column changes no output bit; with a body group on
+ *   and dtables NULL or zero on its columns the outputs are those of the default mask, bit for bit (the body term adds exact zeros).
  * Outputs (NULL = not written), time-major like tsim_rollout's with the direction outermost:
  *   dq_out, dqd_out [ndir][num_frames][B][ndof_r];  dvar_out [ndir][num_frames][B][ndof_var];
  *   dtac_out [ndir][num_masked][B][ndof_tactile] (tactile_slot as in tsim_rollout).
@@ -188,11 +197,17 @@ int tsim_backward_episode(tsim_batch* b, int num_frames, int num_steps, const in
  * limits give the one-sided derivative of the piece each point is on.  BDF2 sub-steps (tape record >= 2) carry the tangents of the two states
  * before them: kv = -4/3 dq0 + 1/3 dq_1, mv = 8h/9 dqd0 - 2h/9 dqd_1, s = K kv + M mv + ..., dq1 = y - kv.  At a frame's end dq, dqd are
  * written, dvar = J_var dq, and every loaded taxel emits A^T R_PA^T (Jx dx + Jv dxd - dth x F + dF/dp_sensor dp); an unloaded taxel an exact 0.
+ * The body columns enter a sub-step's source only through the residual, -(dg/dp) dp linearised at the taped state (the transpose of the body
+ * groups' gradient): per link dF_i = dI_i A_i + V_i x* dI_i V_i for the direction's mass, centre of mass and inertia, with the sub-step's discrete
+ * acceleration as the gradient pass forms it, and s_j -= W_j . (sum of dF_i over the subtree of dof j) / ca, massless intermediate links of a
+ * free3d joint included; per motor s_j += dtau / ca on its dof, dtau = (1 - c) dlo + c dhi with c = (clip(u, -1, 1) + 1) / 2 under force control
+ * (P, D: exactly 0), dtau = (u - q) dP - qd dD under position control (lo, hi: exactly 0); per dof the one-sided derivative of the limit spring's
+ * piece (exactly 0 inside the limits and for k = 0).  A pass of its own (k_tangent_body_src) computes this for all sub-steps before k_tangent.
  * Parameters are the environment's row of tsim_set_env_tables, or the shared model's.  Directions are independent: a direction's bits do
  * not depend on ndir or on the other directions.
  * Returns non-zero (tsim_last_error) and launches nothing for: a null batch; ndir outside 1 .. 8; no tape recorded or a window longer than the
  * tape; a BDF2 model whose window does not start at tape record 0 (no tangent is carried across calls).
- * Out of scope: the body-group columns (TSIM_PG_INERTIAL / MOTOR / LIMIT), geometry and the float header as directions; the fused closed
+ * Out of scope: geometry and the float header as directions; the fused closed
  * loop (tsim_env.h); the B = 1 shim; torch forward-mode AD. */
 enum { TSIM_TANGENT_MAX_DIR = 8 };
 int tsim_tangent_episode(tsim_batch* b, int num_frames, int num_steps, int ndir, const int32_t* tactile_slot,

@@ -458,7 +458,7 @@ struct tsim_batch {
   size_t esz;
   std::vector<CacheEntry> cache;   // saved tapes, newest last
   std::vector<void*> pool;          // spare tape buffers
-  std::vector<void*> retired;       // per-frame pose records replaced by larger ones while a captured graph may still name them (launch_forward)
+  std::vector<void*> retired;       // per-frame pose records (launch_forward) and tangent workspaces (launch_tangent) replaced by larger ones while a captured graph may still name them
   long long* bwd_stamps = nullptr;  // diagnostics (tsim_debug_stamps)
   // tsim_set_param_grad: the caller's table gradient [B][nfrec] (null: off), the adjoint solutions z [cap][B][nr] the adjoint launch saves for the
   // parameter passes, and the contact pass's partial sums [pg_chunks][B][ts_pg_count] (pg_alloc: both when the gradient is first asked for)
@@ -466,6 +466,10 @@ struct tsim_batch {
   // tsim_set_param_grad_groups: which groups of columns a launch adds to (TSIM_PG_*), and the body pass's partial sums
   // [pg_chunks][B][ts_pgb_count] (pg_alloc: once a body group is on and the gradient is asked for)
   int pg_groups = TS_PG_CONTACT; void* pgbpart = nullptr;
+  // tsim_tangent_episode with a body group on: the body columns' part of every sub-step's source, [ndir][n][B][nr] (k_tangent_body_src writes it,
+  // k_tangent reads it).  Grows only: allocated by the first call that needs it or needs it larger (launch_tangent), tan_src_reals its size
+  // tan_src_captured: a launch that names the current workspace was issued under stream capture, so growth retires it instead of freeing it
+  void* tan_src = nullptr; size_t tan_src_reals = 0; int tan_src_captured = 0;
   // the closed-loop adjoint with the buffer set (tsim_push_closed_backward): frame -> seed row of the contact pass, [cap] (pg_alloc; written on the
   // launch's stream by ts_closed_slots_launch)
   int32_t* pg_slots = nullptr;
@@ -787,7 +791,7 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
   const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z || kernel == TS_K_CLOSED_BACKWARD_Z;
-  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
   p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
@@ -1027,6 +1031,7 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
 
 // The tangent pass over the newest T x S taped sub-steps (tsim_tangent_episode): one launch of the generic k_tangent, whatever the batch's view (a
 // compiled-in model's tape has K in its records: a.tk), on the batch's per-environment rows.  Reads the tape, writes the caller's buffers.
+// With a body group on (tsim_set_param_grad_groups) and dtables given, k_tangent_body_src runs first, into the batch's workspace (launch_tangent).
 // the plan of a tangent launch of ndir directions: ts_plan's shape, its LDS grown by the launch's own tangent blocks (ctx_lds: the contexts' part,
 // where the blocks begin).  launch_tangent and tsim_tangent_launch_info both take it from here
 static TsPlan tangent_plan(const tsim_batch* b, int ndir, bool with_dtab, size_t* ctx_lds) {
@@ -1049,7 +1054,37 @@ static int launch_tangent(tsim_batch* b, int T, int S, int ndir, const int32_t* 
   const TsPlan plan = tangent_plan(b, ndir, dtab != nullptr, &ctx_lds);
   a.xoff = (int)(ctx_lds / b->esz);
   if (plan.lds > TS_TAN_LDS_CAP) return fail("tangent_episode: the tangent state of " + std::to_string(ndir) + " directions does not fit the block's LDS for this model");
-  if (!TsLaunch<void, false, R>::run(plan, st, a)) return fail("no k_tangent instantiation for the launch plan");
+  // The body-group columns of dtables (a body group on in tsim_set_param_grad_groups): their part of every sub-step's source by k_tangent_body_src,
+  // over the parameter passes' slots (pg_layout) at the batch's lanes, into the batch's workspace — on this stream, before k_tangent, which adds it
+  if (dtab && (b->pg_groups & ~TS_PG_CONTACT)) {
+    const size_t need = (size_t)ndir * a.n * b->B * b->nr;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if (need > b->tan_src_reals) {      // the one allocation of a tangent call: the first that needs the workspace, or needs it larger
+      if (capturing)
+        return fail("tangent_episode: the body columns' workspace must grow, which a stream capture cannot do: call once with these sizes before capturing");
+      HIPCHK(hipStreamSynchronize(st));          // an earlier launch may still be reading the old workspace
+      // A graph captured from a launch below holds the OLD workspace's address in the arguments of k_tangent_body_src and k_tangent_src — a replay
+      // after this point would write freed memory: such a workspace is retired (freed with the batch), not freed
+      if (b->tan_src_captured) { if (b->tan_src) b->retired.push_back(b->tan_src); b->tan_src_captured = 0; }
+      else (void)hipFree(b->tan_src);
+      b->tan_src = nullptr; b->tan_src_reals = 0;
+      if (hipMalloc(&b->tan_src, need * b->esz) != hipSuccess) { (void)hipGetLastError(); b->tan_src = nullptr; return fail("tangent_episode: hipMalloc of the body columns' workspace failed"); }
+      b->tan_src_reals = need;
+    }
+    const PgLayout lay = pg_layout(b, a.n);
+    TanBodyArgs<R> p{};
+    p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = a.n; p.t_end = b->t_cur;
+    p.tape = (const R*)b->tape; p.nchunk = lay.nchunk; p.chunk_len = lay.chunk_len; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
+    p.groups = b->pg_groups; p.ndir = ndir; p.dtab = (const R*)dtab; p.src = (R*)b->tan_src;
+    if (capturing) b->tan_src_captured = 1;      // a graph now names this workspace
+    TsPlan bp = ts_plan(b, TS_K_TANGENT_BODY, false, 0);
+    bp.grid *= p.nchunk;
+    if (!TsLaunch<void, false, R>::run(bp, st, p)) return fail("no k_tangent_body_src instantiation for the launch plan");
+    HIPCHK(hipGetLastError());
+    a.src = (const R*)b->tan_src;
+  }
+  if (!(a.src ? TsLaunch<void, false, R>::run_tangent_src(plan, st, a) : TsLaunch<void, false, R>::run(plan, st, a))) return fail("no k_tangent instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1135,7 +1170,7 @@ void tsim_batch_destroy(tsim_batch* b) {
   for (auto& k : b->kt) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
   for (hipEvent_t e : b->kt_free) (void)hipEventDestroy(e);
   (void)hipFree(b->dFenv); (void)hipFree(b->dI); (void)hipFree(b->dF); (void)hipFree(b->tape); (void)hipFree(b->lamq); (void)hipFree(b->lamv); (void)hipFree(b->evals); (void)hipFree(b->helped); (void)hipFree(b->gnorm); (void)hipFree(b->order); (void)hipFree(b->order_ep); (void)hipFree(b->prev); (void)hipFree(b->poseR); (void)hipFree(b->poseD); (void)hipFree(b->fposeR); (void)hipFree(b->fposeD); (void)hipFree(b->dKmask); (void)hipFree(b->dFlag);
-  (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); (void)hipFree(b->pgbpart); (void)hipFree(b->pg_slots);
+  (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); (void)hipFree(b->pgbpart); (void)hipFree(b->pg_slots); (void)hipFree(b->tan_src);
   delete b;
 }
 

@@ -32,4 +32,17 @@ template <class R> struct TanArgs {
   const R* tape;
   const R *du, *dq0, *dqd0, *dtab;                           // [ndir][nframes][B][nu], [ndir][B][nr] x 2, [ndir][B][fstride]; null: zeros
   R *dq_out, *dqd_out, *dvar_out, *dtac_out;                 // [ndir][nframes][B][.], dtac_out [ndir][n_masked][B][3 ntax]; null: not written
+  const R* src;                                              // [ndir][n][B][nr]: the body columns' part of the source, -(dg/dp_body) dp_d per sub-step
+                                                             // (k_tangent_body_src wrote it); null: none
+};
+
+// The body-group columns as directions (tsim_set_param_grad_groups: TSIM_PG_INERTIAL / MOTOR / LIMIT on, dtables given): their part of a sub-step's
+// source depends on the taped state only, not on the tangents, so a pass of its own computes it for every sub-step at once before k_tangent runs
+// (k_tangent_body_src, tsim_tangent_body.hip) — on the parameter passes' scaffold (PgCommon, tsim_param_pass.h: a slot is (environment, chunk of
+// sub-steps); z, part and P are not used) — and k_tangent adds it where a direction's TB is finished.  It is k_param_grad_body read forwards.
+template <class R> struct TanBodyArgs : PgCommon<R> {
+  int groups;                                                // TS_PG_*: the body groups whose columns are read
+  int ndir;
+  const R* dtab;                                             // [ndir][B][fstride]
+  R* src;                                                    // [ndir][n][B][nr], sub-step j of the launch's n at row j
 };

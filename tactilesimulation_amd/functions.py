@@ -249,16 +249,24 @@ def episode_jacobian(sim, num_frames, num_steps, columns, tactile_mask=None, out
     BatchedEpisodicParamSimFunction's table gradient (which gives one row J^T w per backward pass; this gives J column by column).
 
     sim holds the tape of the newest num_frames x num_steps sub-steps (reset(backward_flag=True) + rollout, e.g. the forward of
-    BatchedEpisodicParamSimFunction with grad_mode); columns: entries of sim.model.param_columns() — (kind, name, field, column) — or plain
-    column indices, all among the contact columns (BatchSim.tangent_episode reads no other).  One unit direction per column, eight per launch
+    BatchedEpisodicParamSimFunction with grad_mode); columns: entries of sim.model.param_columns() or sim.model.body_param_columns() — (kind,
+    name, field, column) — or plain column indices: the contact columns, and those body columns whose group ('inertial': link mass, centre of
+    mass, inertia; 'motor': lo hi P D; 'limit': lo hi k) is on in sim.param_grad_groups() — BatchSim.tangent_episode reads no other, so a body
+    column whose group is off is refused rather than answered with zeros.  One unit direction per column, eight per launch
     (include/tsim.h tsim_tangent_episode); the tape, the state and the carried adjoint are left as they are, so the episode's backward pass may
     follow.  Returns [B, n_out, len(columns)] with n_out the outputs named in `outputs`, each flattened frame-major ([T, dim], tactile:
     [n_masked, dim]) and concatenated in the order q, var, tactile."""
     cols = [int(c[3]) if isinstance(c, (tuple, list)) else int(c) for c in columns]
     allowed = {int(c) for (_, _, _, c) in sim.model.param_columns()}
-    bad = [c for c in cols if c not in allowed]
+    group_of = {int(c): {"link": "inertial"}.get(kind, kind) for (kind, _, _, c) in sim.model.body_param_columns()}
+    on = set(sim.param_grad_groups())
+    bad = [c for c in cols if c not in allowed and c not in group_of]
     if bad:
-        raise ValueError("episode_jacobian: columns %s are not among model.param_columns()" % bad)
+        raise ValueError("episode_jacobian: columns %s are not among model.param_columns() or model.body_param_columns()" % bad)
+    off = sorted({group_of[c] for c in cols if c in group_of and group_of[c] not in on})
+    if off:
+        raise ValueError("episode_jacobian: columns %s belong to the body group(s) %s, which the tangent pass reads only once they are on: "
+                         "sim.set_param_grad_groups(%r)" % ([c for c in cols if group_of.get(c) in off], off, tuple(sorted(on | set(off)))))
     ntab = sim.base_tables().shape[1]
     keys = [k for k in ("q", "var", "tactile") if k in outputs and (k == "q" or getattr(sim, "ndof_" + k))]
     blocks = []

@@ -224,7 +224,10 @@ class BatchSim:
         """Forward-mode tangent of the newest num_frames env-steps (num_steps sub-steps each) in one launch (include/tsim.h tsim_tangent_episode):
         J v where backward_episode + get_adjoint + set_param_grad give J^T w.  Directions, leading dimension ndir (1 .. 8, taken from the inputs
         given, which must agree; all None: one zero direction): du [ndir, T, B, ndof_u], dq0 / dqd0 [ndir, B, ndof_r] (the tangent of the state
-        at the window's start), dtables [ndir, B, table_size] (only the columns of model.param_columns() are read).  Returns a dict dq [ndir, T, B,
+        at the window's start), dtables [ndir, B, table_size] (the columns of model.param_columns() are read, and those of
+        model.body_param_columns() whose group — 'inertial', 'motor', 'limit' — is on in set_param_grad_groups; no other entry, and with the default
+        groups a body column changes no output bit.  The first call with a body group on, or one larger than any before, allocates the batch's
+        workspace for the body term and synchronises; capture a launch only after such a warm-up call).  Returns a dict dq [ndir, T, B,
         ndof_r], dqd (want_qd), dvar [ndir, T, B, ndof_var], dtactile [ndir, n_masked, B, ndof_tactile].  The tape, the state and the carried adjoint
         are left as they are."""
         T = int(num_frames)

@@ -207,8 +207,8 @@ int tsim_backward_episode(tsim_batch* b, int num_frames, int num_steps, const in
  * not depend on ndir or on the other directions.
  * Returns non-zero (tsim_last_error) and launches nothing for: a null batch; ndir outside 1 .. 8; no tape recorded or a window longer than the
  * tape; a BDF2 model whose window does not start at tape record 0 (no tangent is carried across calls).
- * Out of scope: geometry and the float header as directions; the fused closed
- * loop (tsim_env.h); the B = 1 shim; torch forward-mode AD. */
+ * The fused closed loop has its own entry point, tsim_push_closed_tangent (tsim_env.h): the same sub-steps, a frame's du from the policy's tangent.
+ * Out of scope: geometry and the float header as directions; the B = 1 shim; torch forward-mode AD. */
 enum { TSIM_TANGENT_MAX_DIR = 8 };
 int tsim_tangent_episode(tsim_batch* b, int num_frames, int num_steps, int ndir, const int32_t* tactile_slot,
                          const void* du, const void* dq0, const void* dqd0, const void* dtables,

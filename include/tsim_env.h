@@ -87,6 +87,40 @@ int tsim_push_closed_backward(tsim_batch* b, const tsim_push_policy* pol, const 
                               const void* df_dq, const void* df_dvar, const void* du_direct, const void* u_out, const void* h1_out, const void* h2_out,
                               void* g1_out, void* g2_out, void* g3_out, void* dobs_tac, void* df_du, void* stream);
 
+/* Forward-mode tangent (J v) of that episode, the transpose of tsim_push_closed_backward: per direction d (ndir = 1 .. TSIM_TANGENT_MAX_DIR per
+ * launch, direction outermost in every array, as in include/tsim.h tsim_tangent_episode) the derivative of every frame's q, qd, var and tactile
+ * frame, of the policy's pre-tanh output and of the applied action, along
+ *   dtables [ndir][B][tsim_table_size] (the columns tsim_tangent_episode reads: contact, and the body groups that are on), dq0 / dqd0 [ndir][B][7]
+ *   (tangent of the state at the window's start), dact [ndir][T][B][6] (added to the applied action's tangent), dtac0 [ndir][B][390] (tangent of
+ *   the tactile part of the FIRST observation: tac0 is a caller input of the roll-out, and this is the transpose of dobs_tac[0]), and the
+ *   per-layer sources s1, s2 [ndir][T][B][64], s3 [ndir][T][B][3] on the layers' pre-activations, which carry a direction in the policy's
+ *   parameters: s_l[t] = dW_l x_l[t] + db_l (x_1 the observation, x_2 = h1, x_3 = h2) — the transpose of dW_l = sum_t g_l[t]^T x_l[t].
+ * Every input may be NULL (zeros).  The sub-steps are those of tsim_tangent_episode; what differs is where a frame's du comes from.  At the start
+ * of frame f, with dq the tangent state there and yaw, (gx, gy), (ox, oy) the taped state before the frame, the goal and the box position:
+ *   dgl      = ((-sn gx + cs gy) dq[0] - dq[1], (-cs gx - sn gy) dq[0] - dq[2], -dq[0])                  sn, cs = sin, cos yaw
+ *   dobs_f   = [dgl, dtac_{f-1}]     (no_tactile: dgl;  privilege: [d(box pose in the gripper frame), dgl], the same pattern with (ox, oy) and dq[3], dq[4], dq[6])
+ *   dh1      = elu'(h1_f) (W1 dobs_f + s1_f),   dh2 = elu'(h2_f) (W2 dh1 + s2_f)                          elu' from the recorded outputs
+ *   dupol_f  = W3 dh2 + s3_f                                                                                tangent of the recorded pre-tanh u_out
+ *   du_f     = [(1 - tanh(u_f)^2) dupol_f, 0, 0, 0] + dact_f                                                what the frame's sub-steps use
+ * Frame 0: the goal / pose part of the first observation has tangent ZERO (the adjoint does not propagate the first observation's dependence
+ * on the initial state either) and its tactile part is dtac0.  dtac_{f-1} is what the launch itself wrote to dtac_out[d][f - 1] at the end of
+ * the frame before: with the tactile observation dtac_out is required (workspace and result, like dobs_tac); the last frame's row is written and
+ * observed by nobody.  Outputs, each may be NULL (not written) but for that: dq_out, dqd_out [ndir][T][B][7], dvar_out [ndir][T][B][6], dtac_out
+ * [ndir][T][B][390], dupol_out [ndir][T][B][3], du_out [ndir][T][B][6] (what tsim_tangent_episode would take as du to reproduce the sim half).
+ * The call reads the tape and the records and writes the caller's buffers, nothing else: the tape is not popped, the state, the carried adjoint,
+ * the cache and the pose records are untouched; it may be called any number of times between the roll-out and tsim_push_closed_backward, which
+ * then returns the bits it would have returned without.  No host synchronisation and no allocation, except the body columns' workspace under
+ * tsim_tangent_episode's rules (grows only; refused under stream capture).  A direction's bits depend neither on ndir nor on the other
+ * directions.  Returns non-zero and launches nothing for: a null batch or policy, ndir out of range, no tape or a window longer than it, a policy
+ * with obs_mean set, the tactile observation with dtac_out NULL.  Generic kernels (k_closed_tangent) whatever tsim_kernel_variant reports. */
+int tsim_push_closed_tangent(tsim_batch* b, const tsim_push_policy* pol, const void* goal, int num_frames, int num_steps, int ndir,
+                             const void* u_out, const void* h1_out, const void* h2_out,
+                             const void* s1, const void* s2, const void* s3,
+                             const void* dact, const void* dtac0, const void* dq0, const void* dqd0, const void* dtables,
+                             void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, void* dupol_out, void* du_out, void* stream);
+/* The launch shape of that call with ndir directions, as tsim_tangent_launch_info: out[0..3] = dynamic LDS bytes, block size, grid, lanes per environment. */
+int tsim_push_closed_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

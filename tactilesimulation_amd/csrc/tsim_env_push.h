@@ -233,3 +233,54 @@ extern "C" int tsim_push_closed_backward(tsim_batch* b, const tsim_push_policy* 
   pose_invalidate(b, (hipStream_t)stream);
   return 0;
 }
+
+// ================================================================================================ tangent pass through the closed loop
+// (tsim_tangent_closed.hip k_closed_tangent: k_tangent's walk with the policy's tangent at every frame start; include/tsim_env.h)
+template <class R>
+static int push_closed_tangent_t(tsim_batch* b, const tsim_push_policy* pol, const void* goal, int nframes, int nsub, int ndir, const void* u_out, const void* h1_out,
+                                 const void* h2_out, const void* s1, const void* s2, const void* s3, const void* dact, const void* dtac0, const void* dq0, const void* dqd0,
+                                 const void* dtab, void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, void* dupol_out, void* du_out, hipStream_t st) {
+  TanClosedArgs<R> a{};
+  tangent_args<R>(b, a, nframes, nsub, ndir, nullptr, nullptr, dq0, dqd0, dtab, dq_out, dqd_out, dvar_out, dtac_out);
+  a.pol = make_push_policy<R>(pol);
+  a.pol.goal = (const R*)goal; a.pol.u_out = (R*)u_out; a.pol.h1_out = (R*)h1_out; a.pol.h2_out = (R*)h2_out;      // (read only here)
+  a.s1 = (const R*)s1; a.s2 = (const R*)s2; a.s3 = (const R*)s3; a.dact = (const R*)dact; a.dtac0 = (const R*)dtac0;
+  a.dupol_out = (R*)dupol_out; a.du_out = (R*)du_out;
+  size_t ctx_lds;
+  const TsPlan plan = tangent_plan(b, ndir, dtab != nullptr, &ctx_lds, TS_K_CLOSED_TANGENT);
+  a.xoff = (int)(ctx_lds / b->esz);
+  if (plan.lds > TS_TAN_LDS_CAP) return fail("push_closed_tangent: the tangent state of " + std::to_string(ndir) + " directions does not fit the block's LDS");
+  if (int rc = launch_tangent_body_src<R>(b, a, st, "push_closed_tangent")) return rc;      // body groups on and dtables given: k_tangent_body_src first, unchanged
+  if (!TsLaunch<void, false, R>::run_closed_tangent(plan, st, a)) return fail("no k_closed_tangent instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int tsim_push_closed_tangent(tsim_batch* b, const tsim_push_policy* pol, const void* goal, int num_frames, int num_steps, int ndir,
+                                        const void* u_out, const void* h1_out, const void* h2_out, const void* s1, const void* s2, const void* s3,
+                                        const void* dact, const void* dtac0, const void* dq0, const void* dqd0, const void* dtables,
+                                        void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, void* dupol_out, void* du_out, void* stream) {
+  if (!b || !pol) return fail("push_closed_tangent: null batch / policy");
+  if (ndir < 1 || ndir > TSIM_TANGENT_MAX_DIR) return fail("push_closed_tangent: ndir must be 1 .. " + std::to_string((int)TSIM_TANGENT_MAX_DIR) + ", got " + std::to_string(ndir));
+  if (pol->obs_mean || pol->obs_istd) return fail("push_closed_tangent: a policy on normalised observations (obs_mean) is for forward-only launches; the tangent does not go through the normalisation");
+  if (int rc = push_closed_check(b, pol, num_frames, num_steps, "push_closed_tangent")) return rc;
+  if (!b->record || b->t_cur <= 0) return fail("push_closed_tangent: no tape recorded (reset(backward_flag=True), then tsim_push_closed_rollout)");
+  const long long n = (long long)num_frames * num_steps;
+  if (n > b->t_cur) return fail("push_closed_tangent: the window is the newest num_frames x num_steps = " + std::to_string(n) + " taped sub-steps, the tape holds only " + std::to_string(b->t_cur));
+  if (b->I[TSIM_IH_INTEGRATOR] == 2 && n != b->t_cur)
+    return fail("push_closed_tangent: a BDF2 model's window must start at tape record 0 (no tangent is carried across calls); the tape holds " + std::to_string(b->t_cur) + " sub-steps");
+  if (!goal || !u_out || !h1_out || !h2_out) return fail("push_closed_tangent: null pointer (goal and the forward records u, h1, h2 are required)");
+  if (pol->obs_mode == TSIM_PUSH_OBS_TACTILE && !dtac_out) return fail("push_closed_tangent: dtac_out is required with the tactile observation (workspace and result: frame f observes row f - 1)");
+  TS_DEVICE(b);
+  return b->dtype == TSIM_F32 ? push_closed_tangent_t<float>(b, pol, goal, num_frames, num_steps, ndir, u_out, h1_out, h2_out, s1, s2, s3, dact, dtac0, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, dupol_out, du_out, (hipStream_t)stream)
+                              : push_closed_tangent_t<double>(b, pol, goal, num_frames, num_steps, ndir, u_out, h1_out, h2_out, s1, s2, s3, dact, dtac0, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, dupol_out, du_out, (hipStream_t)stream);
+}
+
+extern "C" int tsim_push_closed_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, int32_t* out) {
+  if (!b || !out) return fail("push_closed_tangent_launch_info: null argument");
+  if (ndir < 1 || ndir > TSIM_TANGENT_MAX_DIR) return fail("push_closed_tangent_launch_info: ndir must be 1 .. " + std::to_string((int)TSIM_TANGENT_MAX_DIR));
+  size_t ctx_lds;
+  const TsPlan p = tangent_plan(b, ndir, with_dtables != 0, &ctx_lds, TS_K_CLOSED_TANGENT);
+  out[0] = (int32_t)p.lds; out[1] = TS_WAVE; out[2] = (int32_t)p.grid; out[3] = p.lpe;
+  return 0;
+}

@@ -791,12 +791,12 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
   const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z || kernel == TS_K_CLOSED_BACKWARD_Z;
-  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
   p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
-  if (kernel == TS_K_TANGENT) {
-    // the tangent pass: every slot holds its tangent block behind the contexts (tsim_tangent.h).  The lanes are chosen for TSIM_TANGENT_MAX_DIR
+  if (kernel == TS_K_TANGENT || kernel == TS_K_CLOSED_TANGENT) {
+    // the tangent pass (and its closed-loop twin, whose policy scratch is the contexts' own pair-staging records): every slot holds its tangent block behind the contexts (tsim_tangent.h).  The lanes are chosen for TSIM_TANGENT_MAX_DIR
     // directions with parameters, whatever the launch asks for — the shape must not depend on ndir or on which inputs are given —: where the
     // block's LDS does not hold that, fewer environments share a wavefront.  grid and lds are those of the contexts; launch_tangent adds the
     // launch's own tangent blocks
@@ -1034,56 +1034,68 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
 // With a body group on (tsim_set_param_grad_groups) and dtables given, k_tangent_body_src runs first, into the batch's workspace (launch_tangent).
 // the plan of a tangent launch of ndir directions: ts_plan's shape, its LDS grown by the launch's own tangent blocks (ctx_lds: the contexts' part,
 // where the blocks begin).  launch_tangent and tsim_tangent_launch_info both take it from here
-static TsPlan tangent_plan(const tsim_batch* b, int ndir, bool with_dtab, size_t* ctx_lds) {
-  TsPlan plan = ts_plan(b, TS_K_TANGENT, false, 0);
+static TsPlan tangent_plan(const tsim_batch* b, int ndir, bool with_dtab, size_t* ctx_lds, int kernel = TS_K_TANGENT) {
+  TsPlan plan = ts_plan(b, kernel, false, 0);
   *ctx_lds = plan.lds;
   const int nhist = b->I[TSIM_IH_INTEGRATOR] == 2 ? 4 : 2, P = with_dtab ? ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr) : 0;
   plan.lds += (((size_t)(TS_WAVE / plan.lpe) * ts_tan_slot_reals(b->nr, b->nu, P, nhist, ndir) * b->esz + 15) / 16) * 16;
   return plan;
 }
+// what a tangent launch takes from the batch and the caller (launch_tangent, and the closed-loop launch in tsim_env_push.h)
 template <class R>
-static int launch_tangent(tsim_batch* b, int T, int S, int ndir, const int32_t* tac_slot, const void* du, const void* dq0, const void* dqd0, const void* dtab,
-                          void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, hipStream_t st) {
-  TanArgs<R> a{};
+static void tangent_args(const tsim_batch* b, TanArgs<R>& a, int T, int S, int ndir, const int32_t* tac_slot, const void* du, const void* dq0, const void* dqd0, const void* dtab,
+                         void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out) {
   a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec;
   a.B = b->B; a.n = T * S; a.t_end = b->t_cur; a.nsub = S; a.nframes = T; a.ndir = ndir; a.tk = b->tape_k;
   a.stage_cpt = b->stage_cpt; a.cull = b->pair_cull; a.tac_slot = tac_slot; a.tape = (const R*)b->tape;
   a.du = (const R*)du; a.dq0 = (const R*)dq0; a.dqd0 = (const R*)dqd0; a.dtab = (const R*)dtab;
   a.dq_out = (R*)dq_out; a.dqd_out = (R*)dqd_out; a.dvar_out = (R*)dvar_out; a.dtac_out = (R*)dtac_out;
+}
+// The body-group columns of dtables (a body group on in tsim_set_param_grad_groups): their part of every sub-step's source by k_tangent_body_src,
+// over the parameter passes' slots (pg_layout) at the batch's lanes, into the batch's workspace — on this stream, before the tangent kernel, which
+// adds it (a.src is set).  Nothing to do without dtables or with the contact group alone.  who: the entry point, for the messages
+template <class R>
+static int launch_tangent_body_src(tsim_batch* b, TanArgs<R>& a, hipStream_t st, const char* who) {
+  if (!a.dtab || !(b->pg_groups & ~TS_PG_CONTACT)) return 0;
+  const int ndir = a.ndir;
+  const size_t need = (size_t)ndir * a.n * b->B * b->nr;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  if (need > b->tan_src_reals) {      // the one allocation of a tangent call: the first that needs the workspace, or needs it larger
+    if (capturing)
+      return fail(std::string(who) + ": the body columns' workspace must grow, which a stream capture cannot do: call once with these sizes before capturing");
+    HIPCHK(hipStreamSynchronize(st));          // an earlier launch may still be reading the old workspace
+    // A graph captured from a launch below holds the OLD workspace's address in the arguments of k_tangent_body_src and the tangent kernel — a replay
+    // after this point would write freed memory: such a workspace is retired (freed with the batch), not freed
+    if (b->tan_src_captured) { if (b->tan_src) b->retired.push_back(b->tan_src); b->tan_src_captured = 0; }
+    else (void)hipFree(b->tan_src);
+    b->tan_src = nullptr; b->tan_src_reals = 0;
+    if (hipMalloc(&b->tan_src, need * b->esz) != hipSuccess) { (void)hipGetLastError(); b->tan_src = nullptr; return fail(std::string(who) + ": hipMalloc of the body columns' workspace failed"); }
+    b->tan_src_reals = need;
+  }
+  const PgLayout lay = pg_layout(b, a.n);
+  TanBodyArgs<R> p{};
+  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = a.n; p.t_end = b->t_cur;
+  p.tape = (const R*)b->tape; p.nchunk = lay.nchunk; p.chunk_len = lay.chunk_len; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
+  p.groups = b->pg_groups; p.ndir = ndir; p.dtab = a.dtab; p.src = (R*)b->tan_src;
+  if (capturing) b->tan_src_captured = 1;      // a graph now names this workspace
+  TsPlan bp = ts_plan(b, TS_K_TANGENT_BODY, false, 0);
+  bp.grid *= p.nchunk;
+  if (!TsLaunch<void, false, R>::run(bp, st, p)) return fail("no k_tangent_body_src instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  a.src = (const R*)b->tan_src;
+  return 0;
+}
+template <class R>
+static int launch_tangent(tsim_batch* b, int T, int S, int ndir, const int32_t* tac_slot, const void* du, const void* dq0, const void* dqd0, const void* dtab,
+                          void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, hipStream_t st) {
+  TanArgs<R> a{};
+  tangent_args<R>(b, a, T, S, ndir, tac_slot, du, dq0, dqd0, dtab, dq_out, dqd_out, dvar_out, dtac_out);
   size_t ctx_lds;
   const TsPlan plan = tangent_plan(b, ndir, dtab != nullptr, &ctx_lds);
   a.xoff = (int)(ctx_lds / b->esz);
   if (plan.lds > TS_TAN_LDS_CAP) return fail("tangent_episode: the tangent state of " + std::to_string(ndir) + " directions does not fit the block's LDS for this model");
-  // The body-group columns of dtables (a body group on in tsim_set_param_grad_groups): their part of every sub-step's source by k_tangent_body_src,
-  // over the parameter passes' slots (pg_layout) at the batch's lanes, into the batch's workspace — on this stream, before k_tangent, which adds it
-  if (dtab && (b->pg_groups & ~TS_PG_CONTACT)) {
-    const size_t need = (size_t)ndir * a.n * b->B * b->nr;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    if (need > b->tan_src_reals) {      // the one allocation of a tangent call: the first that needs the workspace, or needs it larger
-      if (capturing)
-        return fail("tangent_episode: the body columns' workspace must grow, which a stream capture cannot do: call once with these sizes before capturing");
-      HIPCHK(hipStreamSynchronize(st));          // an earlier launch may still be reading the old workspace
-      // A graph captured from a launch below holds the OLD workspace's address in the arguments of k_tangent_body_src and k_tangent_src — a replay
-      // after this point would write freed memory: such a workspace is retired (freed with the batch), not freed
-      if (b->tan_src_captured) { if (b->tan_src) b->retired.push_back(b->tan_src); b->tan_src_captured = 0; }
-      else (void)hipFree(b->tan_src);
-      b->tan_src = nullptr; b->tan_src_reals = 0;
-      if (hipMalloc(&b->tan_src, need * b->esz) != hipSuccess) { (void)hipGetLastError(); b->tan_src = nullptr; return fail("tangent_episode: hipMalloc of the body columns' workspace failed"); }
-      b->tan_src_reals = need;
-    }
-    const PgLayout lay = pg_layout(b, a.n);
-    TanBodyArgs<R> p{};
-    p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = a.n; p.t_end = b->t_cur;
-    p.tape = (const R*)b->tape; p.nchunk = lay.nchunk; p.chunk_len = lay.chunk_len; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
-    p.groups = b->pg_groups; p.ndir = ndir; p.dtab = (const R*)dtab; p.src = (R*)b->tan_src;
-    if (capturing) b->tan_src_captured = 1;      // a graph now names this workspace
-    TsPlan bp = ts_plan(b, TS_K_TANGENT_BODY, false, 0);
-    bp.grid *= p.nchunk;
-    if (!TsLaunch<void, false, R>::run(bp, st, p)) return fail("no k_tangent_body_src instantiation for the launch plan");
-    HIPCHK(hipGetLastError());
-    a.src = (const R*)b->tan_src;
-  }
+  if (int rc = launch_tangent_body_src<R>(b, a, st, "tangent_episode")) return rc;
   if (!(a.src ? TsLaunch<void, false, R>::run_tangent_src(plan, st, a) : TsLaunch<void, false, R>::run(plan, st, a))) return fail("no k_tangent instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   return 0;

@@ -1,20 +1,22 @@
 // tsim_launch.h — launch plans of the simulation kernels and the one launcher that runs them.
 //
 // A plan (TsPlan, made by tsim_hip.hip ts_plan and nowhere else) names one instantiation of k_forward, k_backward, k_backward_z, k_closed_backward_z, k_debug_eval,
-// k_frame_records, k_param_grad, k_param_grad_body, k_tangent or k_tangent_body_src and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
-// (tsim_hip.hip; the parameter passes: tsim_param_grad.hip, tsim_param_grad_body.hip; the tangent pass: tsim_tangent.hip, tsim_tangent_body.hip), or a compiled-in model (tsim_static.h), whose translation units hold nothing but the
+// k_frame_records, k_param_grad, k_param_grad_body, k_tangent, k_tangent_body_src or k_closed_tangent and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
+// (tsim_hip.hip; the parameter passes: tsim_param_grad.hip, tsim_param_grad_body.hip; the tangent pass: tsim_tangent.hip, tsim_tangent_body.hip, tsim_tangent_closed.hip), or a compiled-in model (tsim_static.h), whose translation units hold nothing but the
 // explicit instantiations of TsLaunch for their view: they are built with flags of their own (host/buildhash.py HIP_UNITS).
 #pragma once
 #include <type_traits>
 #include "tsim_kernels.h"
 #include "tsim_param_grad.h"
 #include "tsim_tangent.h"
+#include "tsim_tangent_closed.h"
 #include "tsim_static_pusher.h"
 
 enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD, TS_K_PARAM_GRAD_BODY, TS_K_FRAME_RECORDS,
                 TS_K_CLOSED_BACKWARD_Z,        // the closed-loop adjoint that saves z (k_closed_backward_z): POLICY launches only
                 TS_K_TANGENT,                  // the forward-mode tangent pass (k_tangent, tsim_tangent.hip): generic view only
-                TS_K_TANGENT_BODY };           // its pre-pass for the body-group columns (k_tangent_body_src, tsim_tangent_body.hip): generic view only
+                TS_K_TANGENT_BODY,             // its pre-pass for the body-group columns (k_tangent_body_src, tsim_tangent_body.hip): generic view only
+                TS_K_CLOSED_TANGENT };         // the tangent pass through the fused closed loop (k_closed_tangent, tsim_tangent_closed.hip): generic view only, TactilePush (NRM 8)
 // the view of a launch: the generic kernels, a compiled-in model fully static, or its structure-static twin (parameters at run time)
 enum { TS_KM_GENERIC = 0, TS_KM_STATIC = 1, TS_KM_PARAM = 2 };
 using TsParamPusher = TsParam<TsStaticPusher>;
@@ -39,6 +41,7 @@ template <class MS> constexpr int ts_view_nrm() { return ts_static_nr<MS>() == 0
 // twin of the forward kernel at fp32 and 16 lanes, and there its k_forward_fr twin; k_frame_records wherever a FUSED compiled-in model has a forward kernel.
 constexpr bool ts_instantiated(int kernel, int ms_nrm, bool fp32, bool policy, bool default_opts, int nrm, bool expj, int lpe) {
   if ((expj && (nrm != 16 || lpe != 64)) || (nrm != 8 && nrm != 16) || (lpe != 16 && lpe != 32 && lpe != 64)) return false;
+  if (kernel == TS_K_CLOSED_TANGENT) return ms_nrm == 0 && !policy && !default_opts && nrm == 8 && !expj;      // (launched through the POLICY = false launcher: the policy is the kernel's own)
   if (policy != (kernel == TS_K_CLOSED_BACKWARD_Z) && kernel != TS_K_FORWARD && kernel != TS_K_BACKWARD) return false;
   if (policy && (nrm != 8 || expj)) return false;
   if (ms_nrm == 0) return !default_opts && kernel != TS_K_FRAME_RECORDS;
@@ -53,6 +56,7 @@ template <class R, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE
 template <class R, int NRM, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_tangent(TanArgs<R> a);      // tsim_tangent.hip
 template <class R, int NRM, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_tangent_src(TanArgs<R> a);      // tsim_tangent_body.hip: k_tangent that adds TanArgs::src
 template <class R, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_tangent_body_src(TanBodyArgs<R> a);      // tsim_tangent_body.hip
+template <class R, int NRM, bool EXPJ, int LPE, bool SRC> __global__ void __launch_bounds__(TS_WAVE) k_closed_tangent(TanClosedArgs<R> a);      // tsim_tangent_closed.hip
 
 template <int N> using TsInt = std::integral_constant<int, N>;
 template <bool B> using TsBool = std::integral_constant<bool, B>;
@@ -82,6 +86,7 @@ template <class MS, bool POLICY, class R> struct TsLaunch {
   static bool run(const TsPlan& p, hipStream_t st, const TanArgs<R>& a);
   static bool run(const TsPlan& p, hipStream_t st, const TanBodyArgs<R>& a);
   static bool run_tangent_src(const TsPlan& p, hipStream_t st, const TanArgs<R>& a);      // TS_K_TANGENT with a.src given: k_tangent_src (a member of its own: instantiated in tsim_tangent_body.hip)
+  static bool run_closed_tangent(const TsPlan& p, hipStream_t st, const TanClosedArgs<R>& a);      // TS_K_CLOSED_TANGENT, SRC = (a.src given) (instantiated in tsim_tangent_closed.hip)
 };
 
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a) {
@@ -127,6 +132,12 @@ template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(cons
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run_tangent_src(const TsPlan& p, hipStream_t st, const TanArgs<R>& a) {
   return shape<TS_K_TANGENT>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_tangent_src<R, nrm, expj, lpe>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
 }
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run_closed_tangent(const TsPlan& p, hipStream_t st, const TanClosedArgs<R>& a) {
+  return shape<TS_K_CLOSED_TANGENT>(p, [&](auto nrm, auto expj, auto lpe) {
+    if (a.src) hipLaunchKernelGGL((k_closed_tangent<R, nrm, expj, lpe, true>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a);
+    else hipLaunchKernelGGL((k_closed_tangent<R, nrm, expj, lpe, false>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a);
+  });
+}
 
 // ... in the plan's view
 template <bool POLICY, class R, class A, class... Z> bool ts_launch(const TsPlan& p, hipStream_t st, const A& a, Z... z) {
@@ -135,7 +146,7 @@ template <bool POLICY, class R, class A, class... Z> bool ts_launch(const TsPlan
   return TsLaunch<void, POLICY, R>::run(p, st, a, z...);
 }
 // instantiated in their own units: tsim_static_pusher.hip, tsim_param_pusher.hip, their _policy twins, tsim_param_grad.hip, tsim_param_grad_body.hip,
-// tsim_closed_backward_z.hip, tsim_tangent.hip, tsim_tangent_body.hip
+// tsim_closed_backward_z.hip, tsim_tangent.hip, tsim_tangent_body.hip, tsim_tangent_closed.hip
 extern template struct TsLaunch<TsStaticPusher, false, float>;
 extern template struct TsLaunch<TsStaticPusher, false, double>;
 extern template struct TsLaunch<TsStaticPusher, true, float>;
@@ -154,6 +165,8 @@ extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_
 extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const TanBodyArgs<double>&);
 extern template bool TsLaunch<void, false, float>::run_tangent_src(const TsPlan&, hipStream_t, const TanArgs<float>&);
 extern template bool TsLaunch<void, false, double>::run_tangent_src(const TsPlan&, hipStream_t, const TanArgs<double>&);
+extern template bool TsLaunch<void, false, float>::run_closed_tangent(const TsPlan&, hipStream_t, const TanClosedArgs<float>&);
+extern template bool TsLaunch<void, false, double>::run_closed_tangent(const TsPlan&, hipStream_t, const TanClosedArgs<double>&);
 extern template bool TsLaunch<void, true, float>::run_closed_z(const TsPlan&, hipStream_t, const BwdArgs<float>&, float*);
 extern template bool TsLaunch<void, true, double>::run_closed_z(const TsPlan&, hipStream_t, const BwdArgs<double>&, double*);
 void ts_closed_slots_launch(int32_t* slots, int nframes, hipStream_t st);      // tsim_closed_backward_z.hip: slots[f] = f, the last frame -1

@@ -3,13 +3,17 @@
 // are made of it: k_tangent (SRC = false, tsim_tangent.hip), instruction for instruction the kernel it was before the switch existed, and
 // k_tangent_src (SRC = true, tsim_tangent_body.hip), launched only when a body group is on and dtables is given — reading src in the one kernel
 // cost its fp64 instantiations 2 - 8 more spilled vector registers (profiles/r18_tangent_body.md).
+// A second switch, POLICY (with the launch's argument type A = TanClosedArgs), makes k_closed_tangent (tsim_tangent_closed.hip): a frame's du is then
+// not read from TanArgs::du but formed in the slot by the policy's tangent (tsim_tangent_closed.h).  Both switches are `if constexpr`: with POLICY off
+// the body is the one it was.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "tsim_kernels.h"
 #include "tsim_tangent.h"
+#include "tsim_tangent_closed.h"
 
-template <class R, int NRM, bool EXPJ, int LPE, bool SRC>
-__device__ __forceinline__ void ts_tangent_walk(const TanArgs<R>& a) {
+template <class R, int NRM, bool EXPJ, int LPE, bool SRC, bool POLICY = false, class A = TanArgs<R>>
+__device__ __forceinline__ void ts_tangent_walk(const A& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   R* lds = reinterpret_cast<R*>(smem_raw);
   constexpr int NS = TS_WAVE / LPE;
@@ -93,8 +97,11 @@ __device__ __forceinline__ void ts_tangent_walk(const TanArgs<R>& a) {
     TS_SYNC();
     const int fr = j / a.nsub;
     if (j % a.nsub == 0) {                              // a frame begins: its du
-      for (int d = 0; d < ndir; ++d)
-        if (lane < nu) TU[d * DS + lane] = a.du ? a.du[(((size_t)d * T + fr) * B + env) * nu + lane] : R(0);
+      if constexpr (POLICY) ts_closed_policy_tangent<LPE>(c, lane, valid, a, fr, env, TS, TU, DS);      // ... from the policy's tangent, in the slot
+      else {
+        for (int d = 0; d < ndir; ++d)
+          if (lane < nu) TU[d * DS + lane] = a.du ? a.du[(((size_t)d * T + fr) * B + env) * nu + lane] : R(0);
+      }
     }
     // ---- the taped point, once for all directions: K = dg/dq in c.H (seeds (1, 0, 0)), link states and tangents in LDS
     phase1<R, true, EXPJ>(c, lane, R(1), R(0), R(0));

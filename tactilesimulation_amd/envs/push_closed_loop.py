@@ -188,6 +188,108 @@ class FusedPushEpisode:
         l3.weight.grad, l3.bias.grad = torch.bmm(g3.transpose(1, 2), self.h2).sum(0), g3.sum((0, 1))
         return self.loss
 
+    TANGENT_MAX_DIR = 8      # include/tsim.h TSIM_TANGENT_MAX_DIR
+
+    def tangent(self, dtables=None, dq0=None, dqd0=None, dact=None, dtac0=None, dtheta=None, want=("q", "var", "tac"), sources=None):
+        """Forward-mode tangent (J v) of the episode rollout() recorded, through the policy, in one launch (include/tsim_env.h
+        tsim_push_closed_tangent): how every frame's q, variables, tactile frame, policy output and applied action move along up to 8 directions.
+        Valid after a recorded rollout() and before backward(); it reads the tape and the records and changes nothing, so it may be called any
+        number of times and backward() afterwards returns the bits it would have returned without.
+
+        Directions, leading dimension ndir (1 .. 8, taken from the inputs given, which must agree; all None: one zero direction):
+        dtables [ndir, B, table_size] (the columns BatchSim.tangent_episode reads), dq0 / dqd0 [ndir, B, 7] (tangent of the initial state; the
+        first observation's goal / pose part does not follow it, as in backward()), dact [ndir, T, B, 6] (added to the applied action),
+        dtac0 [ndir, B, 390] (tangent of the first observation's tactile part), dtheta: a direction in the policy's parameters — a list of ndir
+        dicts {"W1", "b1", "W2", "b2", "W3", "b3"} (missing keys: zero) or the stacked tensors (dW1 [ndir, 64, nin], db1 [ndir, 64], dW2, db2,
+        dW3, db3) — turned into per-layer sources by policy_direction_sources; sources: (s1, s2, s3) [ndir, T, B, 64 | 64 | 3] given directly
+        (added to dtheta's; entries may be None).
+
+        Returns a dict: dq [ndir, T, B, 7], dvar [ndir, T, B, 6], dtac [ndir, T, B, 390] (if "tac" is wanted or the policy observes it), dqd (if
+        "qd" is wanted), dupol [ndir, T, B, 3] (pre-tanh policy output), du [ndir, T, B, 6] (applied action: what BatchSim.tangent_episode takes
+        as du), and dloss [ndir, B] = sum_t <df_dq, dq> + <df_dvar, dvar> + <du_direct, dupol>: the directional derivative of rollout()'s loss,
+        per environment, from the partials rollout() keeps."""
+        sim, T, B = self.sim, self.T, self.B
+        if not getattr(self, "_recorded", False) or sim.tape_len() != T * self.env.frame_skip:
+            raise RuntimeError("FusedPushEpisode.tangent: needs the tape of a recorded rollout() (call it before backward())")
+        ntab = capi.lib().tsim_table_size(sim._h)
+        ndir = None
+        if dtheta is not None:
+            s = policy_direction_sources([tuple(m.weight.shape) for m in self.lin], dtheta, self.observations(), self.h1, self.h2)
+            sources = s if sources is None else tuple(x if y is None else (y if x is None else x + y) for x, y in zip(s, sources))
+        sources = (None, None, None) if sources is None else tuple(sources)
+        ins = []
+        for t, tail, name in ((dtables, (B, ntab), "dtables"), (dq0, (B, 7), "dq0"), (dqd0, (B, 7), "dqd0"), (dact, (T, B, 6), "dact"), (dtac0, (B, 390), "dtac0"),
+                              (sources[0], (T, B, 64), "s1"), (sources[1], (T, B, 64), "s2"), (sources[2], (T, B, 3), "s3")):
+            if t is None:
+                ins.append(None)
+                continue
+            t = t.to(device=self.dev, dtype=self.dt).contiguous()
+            if t.dim() != len(tail) + 1 or tuple(t.shape[1:]) != tail:
+                raise ValueError("FusedPushEpisode.tangent: %s must be [ndir, %s], got %s" % (name, ", ".join(str(x) for x in tail), tuple(t.shape)))
+            if ndir is not None and t.shape[0] != ndir:
+                raise ValueError("FusedPushEpisode.tangent: %s has %d directions, the other inputs have %d" % (name, t.shape[0], ndir))
+            ndir = int(t.shape[0])
+            ins.append(t)
+        ndir = 1 if ndir is None else ndir
+        if not 1 <= ndir <= self.TANGENT_MAX_DIR:
+            raise ValueError("FusedPushEpisode.tangent: 1 .. %d directions per launch, got %d" % (self.TANGENT_MAX_DIR, ndir))
+        dtab, dq0, dqd0, dact, dtac0, s1, s2, s3 = ins
+        new = lambda d: torch.empty((ndir, T, B, d), device=self.dev, dtype=self.dt)
+        o = {"dq": new(7), "dvar": new(6), "dupol": new(3), "du": new(6)}
+        if "qd" in want:
+            o["dqd"] = new(7)
+        if "tac" in want or self.mode == 0:
+            o["dtac"] = new(390)
+        st = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        capi.check(capi.lib().tsim_push_closed_tangent(sim._h, C.byref(self._pol), _p(self.goal), T, self.env.frame_skip, ndir,
+                                                       _p(self.u), _p(self.h1), _p(self.h2), _p(s1), _p(s2), _p(s3),
+                                                       _p(dact), _p(dtac0), _p(dq0), _p(dqd0), _p(dtab),
+                                                       _p(o["dq"]), _p(o.get("dqd")), _p(o["dvar"]), _p(o.get("dtac")), _p(o["dupol"]), _p(o["du"]), st))
+        o["dloss"] = ((o["dq"] * self.df_dq).sum(3) + (o["dvar"] * self.df_dvar).sum(3) + (o["dupol"] * self.du_direct).sum(3)).sum(1)
+        return o
+
+    def tangent_launch_info(self, ndir=8, with_dtables=True):
+        """The launch shape of tangent() (include/tsim_env.h tsim_push_closed_tangent_launch_info), as BatchSim.tangent_launch_info."""
+        out = (C.c_int32 * 4)()
+        capi.check(capi.lib().tsim_push_closed_tangent_launch_info(self.sim._h, int(ndir), int(bool(with_dtables)), out))
+        return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}
+
+
+_THETA_KEYS = ("W1", "b1", "W2", "b2", "W3", "b3")
+
+
+def policy_direction_sources(lin_shapes, dtheta, obs, h1, h2):
+    """A direction in the policy's parameters as per-layer sources on the pre-activations (FusedPushEpisode.tangent, include/tsim_env.h
+    tsim_push_closed_tangent): s1 = obs @ dW1^T + db1, s2 = h1 @ dW2^T + db2, s3 = h2 @ dW3^T + db3 — the transpose of how backward() assembles
+    the weight gradients from g1, g2, g3 (dW_l = sum_t g_l[t]^T x_l[t], db_l = sum_t g_l[t]).  Pure torch: runs wherever its inputs live.
+
+    lin_shapes: the three weight shapes [(64, nin), (64, 64), (3, 64)]; dtheta: a list of ndir dicts with keys out of W1, b1, W2, b2, W3, b3
+    (missing: zero), or the stacked tensors (dW1 [ndir, 64, nin], db1 [ndir, 64], dW2, db2, dW3, db3); obs [T, B, nin] (FusedPushEpisode
+    .observations()), h1, h2 [T, B, 64] the recorded layer outputs.  Returns (s1 [ndir, T, B, 64], s2 [ndir, T, B, 64], s3 [ndir, T, B, 3])."""
+    shapes = [tuple(s) for s in lin_shapes]
+    if len(shapes) != 3 or shapes[1][1] != shapes[0][0] or shapes[2][1] != shapes[1][0] or obs.shape[-1] != shapes[0][1]:
+        raise ValueError("policy_direction_sources: lin_shapes %s do not chain from an observation of %d" % (shapes, obs.shape[-1]))
+    want = [shapes[0], shapes[0][:1], shapes[1], shapes[1][:1], shapes[2], shapes[2][:1]]
+    if isinstance(dtheta, (list, tuple)) and len(dtheta) and isinstance(dtheta[0], dict):
+        for d in dtheta:
+            bad = set(d) - set(_THETA_KEYS)
+            if bad:
+                raise ValueError("policy_direction_sources: unknown keys %s (known: %s)" % (sorted(bad), _THETA_KEYS))
+        zero = lambda shp: torch.zeros(shp, device=obs.device, dtype=obs.dtype)
+        stacked = [torch.stack([d[k].to(obs) if d.get(k) is not None else zero(shp) for d in dtheta]) for k, shp in zip(_THETA_KEYS, want)]
+    else:
+        stacked = [t.to(obs) for t in dtheta]
+    if len(stacked) != 6:
+        raise ValueError("policy_direction_sources: six tensors (dW1, db1, dW2, db2, dW3, db3), got %d" % len(stacked))
+    nd = stacked[0].shape[0]
+    for t, shp, k in zip(stacked, want, _THETA_KEYS):
+        if tuple(t.shape) != (nd,) + shp:
+            raise ValueError("policy_direction_sources: d%s must be %s, got %s" % (k, (nd,) + shp, tuple(t.shape)))
+    out = []
+    for x, dW, db in ((obs, stacked[0], stacked[1]), (h1, stacked[2], stacked[3]), (h2, stacked[4], stacked[5])):
+        out.append(torch.einsum("tbi,dji->dtbj", x, dW) + db[:, None, None, :])
+    return tuple(out)
+
 
 def train_epoch_fused(ep, optimizer, q0, goal, disturbances, global_episodes, grad_clip=1.0):
     """algorithms/batched_gd.train_epoch with the episode and its adjoint as one launch each (FusedPushEpisode)."""

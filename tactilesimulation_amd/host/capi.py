@@ -64,6 +64,8 @@ _SIGS = {
     "tsim_push_observe": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tsim_push_closed_rollout": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tsim_push_closed_backward": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tsim_push_closed_tangent": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int] + [_vp] * 18),
+    "tsim_push_closed_tangent_launch_info": (C.c_int, [_vp, C.c_int, C.c_int, _ip]),
     "tsim_push_observe_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = sorted(_SIGS)

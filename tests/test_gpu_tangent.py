@@ -144,9 +144,10 @@ def test_identity_against_the_adjoint(name, dtype):
 
 # lanes per environment k_tangent runs at when 16 / 32 / 64 are asked for: a block's LDS holds at most 64 KB, so fp64 TactilePush has no 16-lane
 # shape (four contexts), D'Claw (10 dofs, NRM 16) none below 32 lanes in fp32 and 64 in fp64; box_slide (3 dofs) has every shape in both precisions.
-# Reached here: NRM 8 at 16 / 32 / 64 lanes in both precisions, NRM 16 at 32 (fp32) and 64 lanes (both).  NOT reached by any model of the suite:
-# k_tangent<float, 16, false, 16> and <double, 16, false, 16 / 32> — the contexts of a model of more than 8 dofs do not fit that many to a block
-# (profiles/r17_tangent.md).
+# Reached here: NRM 8 at 16 / 32 / 64 lanes in both precisions, NRM 16 at 32 (fp32) and 64 lanes (both).  k_tangent<float, 16, false, 16> and
+# <double, 16, false, 32> are run by tests/test_gpu_wide_models.py on models of 9 / 10 dofs on few links; <double, 16, false, 16> cannot be
+# reached by any model — four fp64 contexts of 9 or more dofs exceed a block's 64 KB (the census there, tests/test_wide_models.py,
+# profiles/r20_wide_models.md).
 SHAPES = {("pusher", F64): (32, 32, 64), ("pusher", F32): (16, 32, 64), ("dclaw_position_control", F64): (64, 64, 64),
           ("dclaw_position_control", F32): (32, 32, 64), ("box_slide", F64): (16, 32, 64), ("box_slide", F32): (16, 32, 64)}
 

@@ -64,7 +64,8 @@ def _identity(name, dtype, lanes=0, groups=PU.ALL, nd=3, B=5, case=None, envs=No
     tab = PU.table_rows(m, B, dtype == F32, 11)
     TG._roll(sim, tab, q0, qd0, u, S)
     info = sim.tangent_launch_info(nd, True)
-    batch_lanes = sim.launch_info()["lanes_per_env"]                      # the shape of the parameter passes, the pre-pass among them
+    batch = sim.launch_info()                                             # the shape of the parameter passes, the pre-pass among them
+    batch_lanes, variant = batch["lanes_per_env"], sim.kernel_variant()
     sim.set_param_grad_groups(groups)
     try:
         assert sim.tangent_launch_info(nd, True) == info                 # the launch shape does not depend on the mask
@@ -85,7 +86,7 @@ def _identity(name, dtype, lanes=0, groups=PU.ALL, nd=3, B=5, case=None, envs=No
     if STATS:
         with open(STATS, "a") as f:
             f.write("%s | %s\n" % (tag, " ".join("%.4e" % e for e in err.ravel())))
-    return err, dict(info, batch_lanes=batch_lanes)
+    return err, dict(info, batch_lanes=batch_lanes, batch_lds_bytes=batch["lds_bytes"], variant=variant)
 
 
 # ---------------------------------------------------------------------------------------------------- 1. identity against the kernels' own adjoint

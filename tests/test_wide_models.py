@@ -1,0 +1,277 @@
+"""The compact many-dof models of tests/wide_models.py, checked on the CPU.  No GPU.
+
+tests/test_gpu_wide_models.py runs tests/models/wide9.xml and wide10.xml against the fp64 oracle at launch shapes no other model of the suite
+reaches.  Here: every case converges on the oracle and keeps the conditions the models were built for, in every environment (a loaded and slipping
+ground pair with general contact points, loaded taxels, a dof in its limit); the oracle's gradient has every column kind the GPU file's tallies
+ask for; the rows of the Newton matrix of index 9 and above couple with the dofs below; the oracle's adjoint is the derivative of its forward pass
+along a random direction (the procedure and the 1e-3 criterion of tests/test_tangent_yardstick.py); the arithmetic of a block's LDS — which
+shapes the two models reach, that no 11-dof model with what the issue's list asks for fits where wide10 does, and that NO model of 9 or more dofs fits four fp64 environments to a
+block; and the census of the generic kernel instantiations against the kernel table."""
+import copy
+import json
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import tactilesimulation_amd.model.blob as Bl      # noqa: E402
+import param_grad_util as PU      # noqa: E402
+import wide_models as W      # noqa: E402
+from test_tangent_yardstick import _episode      # noqa: E402
+
+B, T, S = W.B_ENVS, W.T_FRAMES, W.SUBSTEPS
+ROWS_SEED = 11      # tests/test_gpu_wide_models.py ROWS_SEED
+
+
+def _rows(m, fp32):
+    return PU.table_rows(m, B, fp32, ROWS_SEED).astype(np.float64)
+
+
+# ---------------------------------------------------------------------------------------------------- the cases
+@pytest.mark.parametrize("name", W.WIDE)
+def test_every_case_converges_and_keeps_its_conditions(name):
+    """bad == 0 on the base model and on the per-environment rows the GPU file uses (both roundings), and on every environment of each: a loaded
+    point of the ground pair on at least half of the sub-steps, a slipping one, a loaded taxel, the limit active"""
+    m, q0, qd0, u, S_ = W.wide_case(name)
+    assert (q0.shape, u.shape, S_) == ((B, m.ndof_r), (B, T, m.ndof_u), S) and m.ndof_var >= 3 and m.ndof_tactile >= 3 * 4
+    ctrl = [int(m.I[int(m.I[Bl.TSIM_IH_OFF_MOTOR]) + k * Bl.TSIM_MI_SIZE + Bl.TSIM_MI_CTRL]) for k in range(m.ndof_u)]
+    assert 0 in ctrl and 1 in ctrl and len(W.limit_dofs(m)) == 1      # a force and a position motor; one revolute dof with a limit spring
+    for e in range(B):
+        for mm in (m, PU.row_model(m, _rows(m, False)[e]), PU.row_model(m, _rows(m, True)[e])):
+            bad, n, loaded, slip, tax, inlim = W.conditions(mm, q0[e], qd0[e], u[e], S)
+            assert bad == 0 and n == T * S, (name, e)
+            assert 2 * loaded >= n and slip >= 1 and tax >= 1 and inlim == n, (name, e, loaded, slip, tax, inlim)
+
+
+@pytest.mark.parametrize("fp64", [True, False], ids=["fp64", "fp32"])
+@pytest.mark.parametrize("name", W.WIDE)
+def test_oracle_gradient_has_the_kinds_the_gpu_tallies_ask_for(name, fp64):
+    """The coverage asserts of the GPU file's table-gradient test, on the oracle's own gradient (zero error): its tallies must hold
+    wide_models.CONTACT_KINDS / BODY_KINDS above their floors, mu from slipping points and taxels, sensor damping from taxels that move along
+    the normal.  All four groups have non-zero gradients: contact, inertial (mass, com, inertia), motor, limit."""
+    import test_gpu_body_param_grad_oracle as BPGO
+    import test_gpu_param_grad_oracle as PGO
+    m, q0, qd0, u, _ = W.wide_case(name)
+    m = copy.deepcopy(m)
+    if fp64:
+        m.F[Bl.TSIM_FH_TOL] = 1e-13
+    w = PU.loss_weights(m, T)
+    rows = _rows(m, not fp64)
+    tc, tb = PGO.Tally(fp64), BPGO.Tally(fp64)
+    for e in range(B):
+        om = PU.row_model(m, rows[e])
+        go, _, bad, states = PU.oracle_cached(om, q0[e], qd0[e], u[e], S, w)[1]
+        gb, _, bad_b, _ = PU.oracle_cached(om, q0[e], qd0[e], u[e], S, w, groups=PU.ALL)[1]
+        assert bad == 0 and bad_b == 0
+        tc.envs += 1
+        tc.add(m, go, go, m.param_columns(), *PGO._states_flags(states, m, om, np.ones(T, bool)), tag=(name, e))
+        tb.envs += 1
+        tb.add(m, gb, gb, name, (name, e))
+    tc.check("cpu", kinds=W.CONTACT_KINDS[name, fp64])
+    tb.check("cpu", W.BODY_KINDS[name])
+    assert {"mass", "com", "inertia", "motor hi", "motor P", "limit k"} <= set(W.BODY_KINDS[name])
+
+
+def test_both_models_together_cover_every_kind():
+    assert set().union(*(W.CONTACT_KINDS[n, True] for n in W.WIDE)) == set(PU.CONTACT_KINDS)
+    assert set().union(*(W.BODY_KINDS[n] for n in W.WIDE)) == set(PU.BODY_KINDS)
+
+
+@pytest.mark.parametrize("name", W.WIDE)
+def test_every_dof_couples_with_the_dofs_above_it(name):
+    """one chain: the inertial part of the oracle's Newton matrix has no zero block between a link's dofs and its ancestors' — for wide10 the row
+    of index 9 (the tail) against the nine dofs below"""
+    from oracle.oracle import OracleSim
+    m, q0, qd0, u, _ = W.wide_case(name)
+    o = OracleSim(m)
+    q1 = q0[0] + m.h * qd0[0]
+    _, H = o.residual(q1, q0[0], qd0[0], u[0, 0], which=0)
+    nr = m.ndof_r
+    assert np.all(np.abs(H[8:, :3]).max(1) > 0), H[8:, :3]                    # the rows of index 8 and above against the sled
+    if nr > 9:
+        assert np.all(np.abs(H[9:, :9]).max(1) > 0) and np.abs(H[9:, 8]).max() > 0      # the tail against everything below, the finger's turn included
+
+
+# ---------------------------------------------------------------------------------------------------- the yardstick
+# the (step, seed) of the draw that each model is compared at: the first that keeps the base's branches (tests/test_tangent_yardstick.py DRAW_USED)
+DRAW_USED = {"wide9": (1e-4, 0), "wide10": (1e-4, 0)}
+
+
+@pytest.mark.parametrize("name", W.WIDE)
+def test_oracle_adjoint_is_the_derivative_of_its_forward_pass(name):
+    """tests/test_tangent_yardstick.py test_oracle_adjoint_satisfies_the_identity_against_its_finite_differences on the wide models: dL/du, dL/dq0
+    and the contact columns' gradient dotted with one random direction against Richardson-extrapolated central differences at Newton tol 1e-13,
+    moved runs on the base's branches at every sub-step, 1e-3.  One deviation from that file's procedure: the control part of the direction is
+    scaled by the size of each control (a position motor's control is its target in metres, a few millimetres here; that file's models take
+    controls of order one) — the criterion and everything else are that file's"""
+    m, q0, qd0, u, _ = W.wide_case(name, 1)
+    m = copy.deepcopy(m)
+    m.F[Bl.TSIM_FH_TOL] = 1e-13
+    q0, qd0, u = q0[0], qd0[0], u[0]
+    w = PU.loss_weights(m, T, 1)
+    cols = [c for (_, _, _, c) in m.param_columns()]
+    L0, (du, lq, lv, g), sig0, bad0 = _episode(m, q0, qd0, u, S, w, True)
+    assert bad0 == 0
+    # (a position motor's control is its target in metres, a force motor's a share of its range: the direction moves each by a tenth of its size)
+    usc = np.maximum(np.abs(u), 1e-4)
+    for h, seed in [(h_, s_) for h_ in (1e-4, 1e-5, 1e-6) for s_ in range(4)]:
+        rng = np.random.default_rng(7 + seed)
+        vu, vq = 0.1 * rng.normal(size=u.shape) * usc, 0.01 * rng.normal(size=q0.shape)
+        vp = np.zeros(m.F.size); vp[cols] = rng.normal(size=len(cols)) * np.maximum(np.abs(m.F[cols]), 1.0)
+        Ls = []
+        for e in (h, -h, h / 2, -h / 2):
+            mm = copy.deepcopy(m)
+            mm.F[cols] = m.F[cols] + e * vp[cols]
+            Lx, _, sx, bx = _episode(mm, q0 + e * vq, qd0, u + e * vu, S, w, False)
+            if bx or not np.array_equal(sx, sig0):
+                break
+            Ls.append(Lx)
+        if len(Ls) == 4:
+            break
+    assert len(Ls) == 4, "no direction of the draw keeps the base's branches: no finite difference across a kink"
+    print("yardstick %s: step %g, seed %d" % (name, h, seed))
+    assert (h, seed) == DRAW_USED[name], (name, h, seed)
+    ad = float((du * vu).sum() + lq @ vq + g[cols] @ vp[cols])
+    fd = (4 * (Ls[2] - Ls[3]) / h - (Ls[0] - Ls[1]) / (2 * h)) / 3
+    scale = abs((du * vu)).sum() + abs(lq * vq).sum() + abs(g[cols] * vp[cols]).sum()
+    assert abs(ad - fd) <= 1e-3 * max(abs(fd), 1e-5 * scale), (name, ad, fd, scale)
+
+
+# ---------------------------------------------------------------------------------------------------- the LDS arithmetic
+def test_no_model_of_nine_or_more_dofs_fits_four_fp64_environments():
+    """k_forward / k_backward / k_backward_z / k_tangent / k_tangent_src <double, 16, false, 16> cannot be reached: four contexts alone, at the
+    smallest context the joint grammar allows for nr dofs (the fewest links — a link carries at most a translational joint's three dofs, and the
+    free3d joints are chains of such links — and no motor; the context grows with nl and nu), exceed a block's 64 KB for every nr of 9 .. 16.
+    The tables, the schedule and the tangent blocks come on top."""
+    assert max(Bl.JOINT_NDOF[j] for j in Bl.JOINT_NDOF if not j.startswith("free3d")) == W.MAX_DOF_PER_LINK
+    for nr in range(9, 17):
+        nl = W.min_links(nr)
+        assert nl * W.MAX_DOF_PER_LINK >= nr > (nl - 1) * W.MAX_DOF_PER_LINK
+        assert W.lds_env_reals(nl + 1, nr, 0, 8) > W.lds_env_reals(nl, nr, 0, 8) <= W.lds_env_reals(nl, nr, 1, 8)      # (rounded up to four reals)
+        assert 4 * W.env_bytes_lower_bound(nr, 8) > W.LDS_CAP, (nr, W.env_bytes_lower_bound(nr, 8))
+    assert W.lds_env_reals(3, 9, 0, 8) == 2220 and W.lds_env_reals(3, 9, 0, 4) == 2352      # (the figures of profiles/r20_wide_models.md)
+    # ... while two fit, and four in fp32: the shapes the wide models are for
+    assert 2 * W.env_bytes_lower_bound(9, 8) < W.LDS_CAP and 4 * W.env_bytes_lower_bound(9, 4) < W.LDS_CAP
+
+
+# lanes per environment when 16 / 32 / 64 are forced, per-environment rows: (batch, k_tangent) — tests/test_gpu_wide_models.py SHAPES
+SHAPES = {("wide9", 4): ((16, 32, 64), (16, 32, 64)), ("wide9", 8): ((32, 32, 64), (32, 32, 64)),
+          ("wide10", 4): ((16, 32, 64), (32, 32, 64)), ("wide10", 8): ((32, 32, 64), (32, 32, 64))}
+
+
+@pytest.mark.parametrize("name", W.WIDE)
+def test_the_shapes_the_models_reach(name):
+    """the restated arithmetic gives the table the GPU file asserts against the library; the sizes are on record"""
+    m = W.wide_model(name)
+    nl = int(m.I[Bl.TSIM_IH_NL])
+    assert (m.ndof_r, nl) == {"wide9": (9, 4), "wide10": (10, 5)}[name]
+    for esz in (4, 8):
+        got = tuple(tuple(f(m, l, esz)[0] if f is W.forced_shape else f(m, l, esz) for l in (16, 32, 64)) for f in (W.forced_shape, W.tangent_shape))
+        assert got == SHAPES[name, esz], (name, esz, got)
+        print("%s %s: context %d bytes, tangent block %d; blocks of 4 / 2 / 1 environments %s, with eight directions %s" % (
+            name, "fp32" if esz == 4 else "fp64", W.lds_env_reals(nl, m.ndof_r, m.ndof_u, esz) * esz, W.tangent_slot_bytes(m, esz),
+            [W.block_bytes(m, n, esz) for n in (4, 2, 1)], [W.block_bytes(m, n, esz) + n * W.tangent_slot_bytes(m, esz) for n in (4, 2, 1)]))
+
+
+def test_wide10_is_as_large_as_it_gets():
+    """wideN: four fp32 environments per block for k_forward / k_backward AND two fp64 environments per block for k_tangent with eight directions
+    and dtables (the plan sizes that shape for four history states: wide_models.tangent_slot_bytes).  wide10 fits the second by a little over
+    2 KB.  NO model of 11 dofs that has what the models must have fits it: a limit needs a one-dof joint, so 11 dofs need 5 links; with two
+    motors, one end-effector variable, the ground pair, the pad's general-primitive pair and its sensor — the fewest of each — the block of two
+    fp64 environments, counted from these numbers alone with no contact point staged and the shortest schedule, exceeds 64 KB (every term is
+    non-decreasing in every count).  Without those requirements 11 dofs would fit: it is the issue's list that makes 10 the largest."""
+    m = W.wide_model("wide10")
+    fits = W.block_bytes(m, 2, 8) + 2 * W.tangent_slot_bytes(m, 8)
+    assert W.LDS_CAP - 3072 < fits <= W.LDS_CAP and W.block_bytes(m, 4, 4) <= W.LDS_CAP, fits
+    # the count-based form is the restated arithmetic: it reproduces both models' blocks
+    for name in W.WIDE:
+        mm = W.wide_model(name)
+        I = mm.I
+        nl, npair, ns, ncpt = (int(I[k]) for k in (Bl.TSIM_IH_NL, Bl.TSIM_IH_NPAIR, Bl.TSIM_IH_NSENSOR, Bl.TSIM_IH_NCPT))
+        for esz, nslot in ((8, 2), (8, 1), (4, 4), (4, 2)):
+            assert W.tangent_block_bytes_of_counts(mm.ndof_r, nl, mm.ndof_u, mm.ndof_var // 3, npair, ns, 1, nl, esz, nslot, ncpt) == \
+                W.block_bytes(mm, nslot, esz) + nslot * W.tangent_slot_bytes(mm, esz), (name, esz, nslot)
+    assert W.min_links(11) == 4 and 3 * W.MAX_DOF_PER_LINK + 1 < 11      # four links with a one-dof joint among them carry 10 dofs at most
+    least = dict(nl=5, nu=2, nvar=1, npair=2, nsensor=1, nsprim=1, nsteps=1)
+    assert W.tangent_block_bytes_of_counts(11, esz=8, nslot=2, **least) > W.LDS_CAP
+    assert W.tangent_block_bytes_of_counts(10, esz=8, nslot=2, **least) <= W.LDS_CAP
+    for k in least:      # non-decreasing in every count
+        assert W.tangent_block_bytes_of_counts(11, esz=8, nslot=2, **dict(least, **{k: least[k] + 1})) >= W.tangent_block_bytes_of_counts(11, esz=8, nslot=2, **least)
+
+
+# ---------------------------------------------------------------------------------------------------- the census
+def _generic_rows(table):
+    """the generic non-policy instantiations of the kernel table: (kernel, real, NRM or None, EXPJ, LPE).  The patterns of
+    tests/test_capi_symbols.py for the four simulation kernels; the parameter passes and the tangent kernels have generic instantiations only"""
+    got = set()
+    for name in table:
+        m = re.match(r"_Z\d+(k_forward|k_backward|k_backward_z)I([fd])Li(\d+)ELb([01])ELi(\d+)ELb([01])E(.+?)Ev7[FB]wdArgs", name)
+        d = re.match(r"_Z\d+k_debug_evalI([fd])Li(\d+)E(.+?)Ev7DbgArgs", name)
+        p = re.match(r"_Z\d+(k_param_grad|k_param_grad_body|k_tangent_body_src)I([fd])Lb([01])ELi(\d+)EEv\d+(Pg|PgBody|TanBody)ArgsI", name)
+        t = re.match(r"_Z\d+(k_tangent|k_tangent_src)I([fd])Li(\d+)ELb([01])ELi(\d+)EEv7TanArgsI", name)
+        if m and m[6] == "0" and m[7] == "v":
+            got.add((m[1], m[2], int(m[3]), m[4] == "1", int(m[5])))
+        elif d and d[3] == "v":
+            got.add(("k_debug_eval", d[1], None, False, int(d[2])))
+        elif p:
+            got.add((p[1], p[2], None, p[3] == "1", int(p[4])))
+        elif t:
+            got.add((t[1], t[2], int(t[3]), t[4] == "1", int(t[5])))
+        else:
+            assert not re.match(r"_Z\d+(k_param_grad|k_param_grad_body|k_tangent|k_tangent_src|k_tangent_body_src)I", name), name
+    return got
+
+
+def _test_runs(path, fn, case, lanes):
+    """Does the test `fn` of tests/`path` run `case` with `lanes` forced?  Read off the test itself: the case (or, for the BDF2 file's own case
+    names, the case without its "bdf2:" prefix) is among the values of its parametrize marks, or a literal of its body, or — where the body
+    loops over param_grad_util.MODELS — one of those; the lanes (0: none forced) are among the values of its marks.  A test that drops the case
+    or the shape fails the census here.  What this cannot see is a test that skips the case at run time: the GPU file's plan test covers the
+    shape, not the named test's execution"""
+    import importlib
+    import inspect
+    f = getattr(importlib.import_module(path[:-3]), fn)
+    vals = []
+    for mk in getattr(f, "pytestmark", []):
+        if mk.name == "parametrize":
+            for v in mk.args[1]:
+                v = getattr(v, "values", v)
+                vals += list(v) if isinstance(v, (tuple, list)) else [v]
+    src = inspect.getsource(f)
+    names = (case, case.split(":")[-1])
+    case_ok = any(n in vals for n in names) or '"%s"' % case in src or ("MODELS" in src and case in [n for n, _ in PU.MODELS])
+    return case_ok and (lanes == 0 or lanes in vals)
+
+
+def test_every_generic_instantiation_is_run_by_a_test_or_cannot_be():
+    """REACHED_BY + UNREACHABLE of tests/test_gpu_wide_models.py = the generic non-policy rows of the kernel table: an instantiation added without
+    a test that runs it fails here.  Every entry names a test of the suite that has the entry's case and forced lanes among its parameters
+    (_test_runs); the shapes of the entries on the repository's own contact-free-of-
+    rotation-vector models are the restated arithmetic's (the GPU file asks the library)."""
+    from tactilesimulation_amd.host import buildhash
+    import test_gpu_wide_models as G
+    if not os.path.exists(buildhash.KERNELS_JSON):
+        import __graft_entry__
+        __graft_entry__.build()
+    got = _generic_rows(json.load(open(buildhash.KERNELS_JSON)))
+    assert len(got) == 100 and not set(G.REACHED_BY) & set(G.UNREACHABLE)
+    assert set(G.REACHED_BY) | set(G.UNREACHABLE) == got, ("no test", sorted(got - set(G.REACHED_BY) - set(G.UNREACHABLE), key=str),
+                                                             "no kernel", sorted((set(G.REACHED_BY) | set(G.UNREACHABLE)) - got, key=str))
+    for inst in G.UNREACHABLE:
+        assert inst[1:] == ("d", 16, False, 16) and 4 * W.env_bytes_lower_bound(9, 8) > W.LDS_CAP, inst
+    for (kernel, r, nrm, expj, lpe), (case, lanes, rows, test) in G.REACHED_BY.items():
+        path, _, fn = test.partition("::")
+        assert _test_runs(path, fn, case, lanes), (test, case, lanes)
+        m = G.census_model(case)
+        assert (nrm is None or nrm == (16 if m.ndof_r > 8 or expj else 8)) and (not expj or lpe == 64), (kernel, r, nrm, expj, lpe)
+        if not expj:
+            esz = 8 if r == "d" else 4
+            shape = W.tangent_shape(m, lanes, esz, rows) if kernel in G.TANGENT_SHAPED else W.forced_shape(m, lanes, esz, rows)[0]
+            assert shape == lpe, (kernel, r, nrm, expj, lpe, case, lanes, shape)
+        # NRM 16 below 64 lanes, and every row at 16 / 32 lanes that the wide models reach, is run by the new file
+        if nrm == 16 and not expj:
+            assert case in W.WIDE and path == "test_gpu_wide_models.py"

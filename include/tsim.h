@@ -219,6 +219,32 @@ int tsim_tangent_episode(tsim_batch* b, int num_frames, int num_steps, int ndir,
  * state of TSIM_TANGENT_MAX_DIR directions with parameters, so they do not depend on ndir or with_dtables; the LDS bytes do. out = int32[4]. */
 int tsim_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, int32_t* out);
 
+/* Per-frame transition Jacobians (no reference counterpart): the local linearisation of the dynamics over the newest num_frames * num_steps taped
+ * sub-steps, every frame in ONE launch.  Frame f is sub-steps f * num_steps .. (f + 1) * num_steps - 1 of that window; with x = (q, qdot):
+ *   A_out    [num_frames][B][2 ndof_r][2 ndof_r]   dx_{f+1} / dx_f: rows (q, qdot) at the frame's end, columns (q, qdot) at its start;
+ *   B_out    [num_frames][B][2 ndof_r][ndof_u]     dx_{f+1} / du_f, u held for the frame's sub-steps; a clipped force control: exactly zero columns;
+ *   Jvar_out [num_frames][B][ndof_var][ndof_r]     dvariables / dq at the frame's END state, the measurement map that goes with x_{f+1}
+ *                                                  (tsim_tangent_episode's dvar = Jvar dq).
+ * Device memory, the batch's real type, row-major; any may be NULL (not written); with A_out and B_out both NULL nothing is solved.  So
+ * x_{f+1} = A_f x_f + B_f u_f to first order, and chaining the frames reproduces tsim_tangent_episode's dq, dqd to round-off.
+ * Per sub-step it is tsim_tangent_episode's BDF1 recursion seeded with the identity, for all 2 ndof_r + ndof_u columns:
+ *     s = -K dq0 + h M dqd0 + D du ,   H y = s ,   dq1 = dq0 + y ,   dqd1 = cv y
+ * with H the taped Newton matrix and K, M, D of the taped point, evaluated once for all columns; the columns are solved eight per elimination of H
+ * (in double, with partial pivoting).  A sub-step that did not converge is treated as the adjoint treats it; limits and stick / slip give the
+ * one-sided derivative of the piece the state is on.  Parameters are the environment's row of tsim_set_env_tables, or the shared model's.  A
+ * frame's matrices depend on that frame's tape records only: their bits depend neither on num_frames nor on which outputs are given (A, B).
+ * Read-only: the tape is not popped; the state, the carried adjoint, the cache and the pose records are untouched.  No allocation, no host
+ * synchronisation; capturable.  A compiled-in model's batch runs the generic evaluation on its tape, as tsim_tangent_episode does.
+ * Returns non-zero (tsim_last_error) and launches nothing for: a null batch; no tape recorded or a window longer than the tape; num_frames or
+ * num_steps < 1; a BDF2 model (its transition acts on two states of history); a model whose block would not fit the 64 KB of LDS.
+ * Out of scope: table columns and geometry as inputs; the tactile Jacobian (ndof_tactile x 2 ndof_r per frame and environment:
+ * tsim_tangent_episode gives its action on a direction); BDF2; the B = 1 shim; the fused closed-loop tape. */
+int tsim_frame_jacobians(tsim_batch* b, int num_frames, int num_steps, void* A_out, void* B_out, void* Jvar_out, void* stream);
+/* Diagnostics: the static launch geometry of a tsim_frame_jacobians call, as tsim_tangent_launch_info reports a tangent call's: out[0] = LDS bytes
+ * per block (the contexts and the slots' column blocks), out[1] = threads per block, out[2] = blocks PER FRAME, out[3] = lanes per environment:
+ * the batch's, doubled until a block fits 64 KB; they do not depend on which outputs are asked for.  out = int32[4]. */
+int tsim_frame_jacobians_launch_info(const tsim_batch* b, int32_t* out);
+
 /* sim.backward() results df_dq0 / df_dqdot0                    envs/redmax_torch_functions.py:92-100
  * = the carried adjoint once the whole tape has been popped. [B][ndof_r] each. */
 int tsim_get_adjoint(tsim_batch* b, void* df_dq0, void* df_dqd0, void* stream);

@@ -891,6 +891,61 @@ __device__ __forceinline__ void solve_newton(const R* A, const R* b, R* x, int n
   solve_lanes<R, NRM, LPE, double>(A, b, x, n, transpose, lane, write);
 }
 
+// ---- many right-hand sides per elimination (k_frame_jacobian, tsim_frame_jacobian.hip) ---------------------------------------------------
+// solve_lanes' elimination — lanes = rows, double, the same pivot key and tie rule — carrying NB right-hand sides per lane in registers: A is
+// eliminated once for all of them.  W holds them column by column, right-hand side k at W[k * n .. k * n + n), and receives the solutions in
+// place; only the first nb (1 .. NB) are read or written.  A x = b only (no transpose), every slot writes.  The multipliers and the pivot order
+// are those solve_lanes finds for the same A, so a column's solution is solve_lanes' for that column, bit for bit.
+template <class R, int NRM, int LPE, int NB>
+__device__ __forceinline__ void solve_lanes_many(const R* A, R* W, int n, int nb, int lane) {
+  const int sbase = (int)threadIdx.x & ~(LPE - 1);
+  auto sbc = [sbase](auto v, int src) { return lane_gather(v, sbase + src); };
+  double a[NRM], rb[NB];
+  const bool row = lane < n;
+  const int r = min(lane, n - 1);
+#pragma unroll
+  for (int j = 0; j < NRM; ++j) {
+    const int jj = min(j, n - 1);
+    const double v = (double)A[r * n + jj];
+    a[j] = (row && j < n) ? v : ((j == lane) ? 1.0 : 0.0);
+  }
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    const double v = (double)W[min(k, nb - 1) * n + r];
+    rb[k] = (row && k < nb) ? v : 0.0;
+  }
+  bool done = !row; int mycol = -1; double mypiv = 1.0;
+#pragma unroll
+  for (int col = 0; col < NRM; ++col) {
+    if (col < n) {
+      unsigned key = done ? 0u : ((__builtin_bit_cast(unsigned, fabsf((float)a[col])) & ~0xFu) | (unsigned)(15 - (lane & 15)) | 0x10u);
+      key = max(key, (unsigned)dpp_i<0xB1, 0xf>((int)key));
+      key = max(key, (unsigned)dpp_i<0x4E, 0xf>((int)key));
+      key = max(key, (unsigned)dpp_i<0x141, 0xf>((int)key));
+      key = max(key, (unsigned)dpp_i<0x140, 0xf>((int)key));
+      const int p = 15 - (int)(sbc((int)key, 0) & 0xFu);
+      double prow[NRM], pb[NB];
+#pragma unroll
+      for (int j = 0; j < NRM; ++j) if (j >= col) prow[j] = sbc(a[j], p);
+#pragma unroll
+      for (int k = 0; k < NB; ++k) pb[k] = sbc(rb[k], p);
+      const double piv = prow[col];
+      const bool isp = lane == p;
+      const double f = isp ? 0.0 : a[col] * fast_rcp(piv);
+#pragma unroll
+      for (int j = 0; j < NRM; ++j) if (j >= col) a[j] -= f * prow[j];
+#pragma unroll
+      for (int k = 0; k < NB; ++k) rb[k] -= f * pb[k];
+      done = done || isp; mycol = isp ? col : mycol; mypiv = isp ? piv : mypiv;
+    }
+  }
+  const double ip = fast_rcp(mypiv);
+#pragma unroll
+  for (int k = 0; k < NB; ++k)
+    if (row && mycol >= 0 && k < nb) W[k * n + mycol] = (R)(rb[k] * ip);
+  TS_SYNC();
+}
+
 template <int LPE, class R> __device__ __forceinline__ R block_norm2(const R* v, int n, int lane) {
   R s = lane < n ? v[lane] * v[lane] : R(0);
   return t_sqrt(seg_sum<LPE>(s));

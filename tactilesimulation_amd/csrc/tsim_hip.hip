@@ -791,7 +791,7 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
   const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z || kernel == TS_K_CLOSED_BACKWARD_Z;
-  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || kernel == TS_K_FRAME_JACOBIAN || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
   p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
@@ -802,6 +802,16 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
     // launch's own tangent blocks
     const size_t most = (size_t)ts_tan_slot_reals(b->nr, b->nu, ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr), 4, TS_TAN_MAX_DIR) * b->esz;
     while (p.lpe < TS_WAVE && lds_bytes_for(b, TS_WAVE / p.lpe) + (TS_WAVE / p.lpe) * most > TS_TAN_LDS_CAP) p.lpe *= 2;
+    const int ns = TS_WAVE / p.lpe;
+    p.grid = (unsigned)((b->B + ns - 1) / ns);
+    p.lds = lds_bytes_for(b, ns);
+  }
+  if (kernel == TS_K_FRAME_JACOBIAN) {
+    // the frame Jacobians: every slot holds its 2 nr + nu columns behind the contexts (tsim_frame_jacobian.h), whichever outputs are asked for; where
+    // the block's LDS does not hold that, fewer environments share a wavefront.  lds is the contexts'; frame_jacobian_plan adds the blocks and
+    // multiplies the grid by the frames
+    const size_t blk = (size_t)ts_fj_slot_reals(b->nr, b->nu) * b->esz;
+    while (p.lpe < TS_WAVE && lds_bytes_for(b, TS_WAVE / p.lpe) + (TS_WAVE / p.lpe) * blk > TS_TAN_LDS_CAP) p.lpe *= 2;
     const int ns = TS_WAVE / p.lpe;
     p.grid = (unsigned)((b->B + ns - 1) / ns);
     p.lds = lds_bytes_for(b, ns);
@@ -1101,6 +1111,32 @@ static int launch_tangent(tsim_batch* b, int T, int S, int ndir, const int32_t* 
   return 0;
 }
 
+// The per-frame transition Jacobians over the newest T x S taped sub-steps (tsim_frame_jacobians): one launch of the generic k_frame_jacobian,
+// T x ceil(B / NS) blocks, whatever the batch's view, on the batch's per-environment rows.  Reads the tape, writes the caller's buffers.
+// the plan: ts_plan's shape for ONE frame, its LDS grown by the slots' blocks (ctx_lds: the contexts' part, where the blocks begin)
+static TsPlan frame_jacobian_plan(const tsim_batch* b, size_t* ctx_lds) {
+  TsPlan plan = ts_plan(b, TS_K_FRAME_JACOBIAN, false, 0);
+  *ctx_lds = plan.lds;
+  plan.lds += (((size_t)(TS_WAVE / plan.lpe) * ts_fj_slot_reals(b->nr, b->nu) * b->esz + 15) / 16) * 16;
+  return plan;
+}
+template <class R>
+static int launch_frame_jacobians(tsim_batch* b, int T, int S, void* A_out, void* B_out, void* Jvar_out, hipStream_t st) {
+  size_t ctx_lds;
+  TsPlan plan = frame_jacobian_plan(b, &ctx_lds);
+  if (plan.lds > TS_TAN_LDS_CAP) return fail("frame_jacobians: the " + std::to_string(ts_fj_ncol(b->nr, b->nu)) + " columns of an environment do not fit the block's LDS for this model");
+  if ((unsigned long long)plan.grid * (unsigned)T > 0x7fffffffull) return fail("frame_jacobians: too many blocks");
+  FjArgs<R> a{};
+  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.n = T * S; a.t_end = b->t_cur;
+  a.tape = (const R*)b->tape; a.nchunk = T; a.chunk_len = S; a.stage_cpt = b->stage_cpt; a.tk = b->tape_k; a.cull = b->pair_cull;
+  a.xoff = (int)(ctx_lds / b->esz);
+  a.A_out = (R*)A_out; a.B_out = (R*)B_out; a.Jvar_out = (R*)Jvar_out;
+  plan.grid *= (unsigned)T;
+  if (!TsLaunch<void, false, R>::run(plan, st, a)) return fail("no k_frame_jacobian instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 const char* tsim_last_error(void) { return g_err.c_str(); }
@@ -1204,6 +1240,13 @@ int tsim_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, in
   if (ndir < 1 || ndir > TSIM_TANGENT_MAX_DIR) return fail("tangent_launch_info: ndir must be 1 .. " + std::to_string((int)TSIM_TANGENT_MAX_DIR));
   size_t ctx_lds;
   const TsPlan p = tangent_plan(b, ndir, with_dtables != 0, &ctx_lds);
+  out[0] = (int32_t)p.lds; out[1] = TS_WAVE; out[2] = (int32_t)p.grid; out[3] = p.lpe;
+  return 0;
+}
+int tsim_frame_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
+  if (!b || !out) return fail("frame_jacobians_launch_info: null argument");
+  size_t ctx_lds;
+  const TsPlan p = frame_jacobian_plan(b, &ctx_lds);
   out[0] = (int32_t)p.lds; out[1] = TS_WAVE; out[2] = (int32_t)p.grid; out[3] = p.lpe;
   return 0;
 }
@@ -1522,6 +1565,19 @@ int tsim_tangent_episode(tsim_batch* b, int num_frames, int num_steps, int ndir,
   TS_DEVICE(b);
   return b->dtype == TSIM_F32 ? launch_tangent<float>(b, num_frames, num_steps, ndir, tactile_slot, du, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, (hipStream_t)stream)
                               : launch_tangent<double>(b, num_frames, num_steps, ndir, tactile_slot, du, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, (hipStream_t)stream);
+}
+
+int tsim_frame_jacobians(tsim_batch* b, int num_frames, int num_steps, void* A_out, void* B_out, void* Jvar_out, void* stream) {
+  if (!b) return fail("frame_jacobians: null batch");
+  if (!b->record || b->t_cur <= 0) return fail("frame_jacobians: no tape recorded (reset(backward_flag=True), then a roll-out)");
+  if (num_frames <= 0 || num_steps <= 0) return fail("frame_jacobians: num_frames and num_steps must be positive");
+  const long long n = (long long)num_frames * num_steps;
+  if (n > b->t_cur) return fail("frame_jacobians: only " + std::to_string(b->t_cur) + " sub-steps on the tape");
+  if (b->I[TSIM_IH_INTEGRATOR] == 2) return fail("frame_jacobians: a BDF2 model's transition acts on two states of history, which is out of scope");
+  if (!A_out && !B_out && !Jvar_out) return 0;
+  TS_DEVICE(b);
+  return b->dtype == TSIM_F32 ? launch_frame_jacobians<float>(b, num_frames, num_steps, A_out, B_out, Jvar_out, (hipStream_t)stream)
+                              : launch_frame_jacobians<double>(b, num_frames, num_steps, A_out, B_out, Jvar_out, (hipStream_t)stream);
 }
 
 int tsim_get_adjoint(tsim_batch* b, void* df_dq0, void* df_dqd0, void* stream) {

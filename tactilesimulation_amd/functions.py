@@ -281,3 +281,22 @@ def episode_jacobian(sim, num_frames, num_steps, columns, tactile_mask=None, out
     if not blocks:
         return torch.zeros((sim.B, 0, 0), device=sim.device, dtype=sim.dtype)
     return torch.cat(blocks, 2)
+
+
+def episode_transition(sim, num_frames, num_steps):
+    """Local linearisation of the recorded episode's dynamics, per environment and env-step: (A, B) with A [T, B, 2 nr, 2 nr] and
+    B [T, B, 2 nr, nu], T = num_frames, x = (q, qd):
+
+        x_{f+1} = A_f x_f + B_f u_f          (to first order around the recorded roll-out; u_f held for the frame's num_steps sub-steps)
+
+    so  dx_T = A_{T-1} ... A_0 dx_0 + sum_f A_{T-1} ... A_{f+1} B_f du_f  — the q-rows of these products are what BatchSim.tangent_episode returns
+    as dq for the direction (dx_0, du), and what episode_jacobian gives column by column for TABLE columns; episode_jacobian differentiates the
+    frames' outputs w.r.t. parameters over the whole episode, this differentiates one frame's end state w.r.t. that frame's start state and
+    control.  What iLQR / DDP, a time-varying LQR or an EKF around a recorded push take; the product of the A_f's spectral norms bounds the growth
+    of a BPTT gradient through the episode.
+
+    sim holds the tape of the newest num_frames x num_steps sub-steps (reset(backward_flag=True) + rollout).  One launch for every frame
+    (include/tsim.h tsim_frame_jacobians); the tape, the state and the carried adjoint are left as they are, so the episode's backward pass may
+    follow.  BDF1 models only."""
+    o = sim.frame_jacobians(num_frames, num_steps, want_A=True, want_B=True, want_var=False)
+    return o["A"], o["B"]

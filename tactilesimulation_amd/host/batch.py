@@ -262,6 +262,25 @@ class BatchSim:
                                                    _ptr(o["dq"]), _ptr(o.get("dqd")), _ptr(o.get("dvar")), _ptr(o.get("dtactile")), self._stream()))
         return o
 
+    def frame_jacobians(self, num_frames, num_steps, want_A=True, want_B=True, want_var=False):
+        """Per-frame transition Jacobians of the newest num_frames env-steps (num_steps sub-steps each) in one launch (include/tsim.h
+        tsim_frame_jacobians), with x = (q, qd): a dict of A [T, B, 2 ndof_r, 2 ndof_r] = dx_{f+1} / dx_f (want_A), B [T, B, 2 ndof_r, ndof_u] =
+        dx_{f+1} / du_f with u held for the frame (want_B; a clipped force control: exactly zero columns) and Jvar [T, B, ndof_var, ndof_r] =
+        dvariables / dq at the frame's end state (want_var).  BDF1 models only.  The tape, the state and the carried adjoint are left as they
+        are; a frame's matrices do not depend on num_frames or on which of A, B are asked for."""
+        T = int(num_frames)
+        n2 = 2 * self.ndof_r
+        new = lambda r, c: torch.empty((T, self.B, r, c), device=self.device, dtype=self.dtype)
+        o = {}
+        if want_A:
+            o["A"] = new(n2, n2)
+        if want_B:
+            o["B"] = new(n2, self.ndof_u)
+        if want_var and self.ndof_var:
+            o["Jvar"] = new(self.ndof_var, self.ndof_r)
+        capi.check(capi.lib().tsim_frame_jacobians(self._h, T, int(num_steps), _ptr(o.get("A")), _ptr(o.get("B")), _ptr(o.get("Jvar")), self._stream()))
+        return o
+
     def get_state(self):
         q, qd = self.empty(self.ndof_r), self.empty(self.ndof_r)
         capi.check(capi.lib().tsim_get_state(self._h, _ptr(q), _ptr(qd), self._stream()))
@@ -399,4 +418,11 @@ class BatchSim:
         wider than the batch's, where a block would not hold the tangent state of eight directions"""
         out = (C.c_int32 * 4)()
         capi.check(capi.lib().tsim_tangent_launch_info(self._h, int(ndir), int(bool(with_dtables)), out))
+        return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}
+
+    def frame_jacobians_launch_info(self):
+        """launch_info() of a frame_jacobians call (include/tsim.h tsim_frame_jacobians_launch_info): blocks PER FRAME; its lanes per environment
+        may be wider than the batch's, where a block would not hold the 2 ndof_r + ndof_u columns of every slot"""
+        out = (C.c_int32 * 4)()
+        capi.check(capi.lib().tsim_frame_jacobians_launch_info(self._h, out))
         return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}

@@ -6,7 +6,8 @@ seed on the last sub-step; a qd-row uses qd_S = (q_S - q_{S-1}) / h (BDF1): +1/h
 the frame's start and goes directly on the q_f column.  That builder is the derivative of the oracle's one-frame map only if it agrees with finite
 differences of that map, so here rows @ v is held against Richardson-extrapolated central differences ((4 D(h/2) - D(h)) / 3 at Newton tol 1e-13)
 along one random direction v in (q_f, qd_f, u_f), with the step, the tolerance (1e-3) and the branch-signature filter of
-tests/test_tangent_yardstick.py: every compared draw keeps the base's signature at every sub-step."""
+tests/test_tangent_yardstick.py: every compared draw keeps the base's signature at every sub-step.  small:11 and small:52 of the random corpus
+are there for their Newton matrices, which pivot off the diagonal on every sub-step of the frame."""
 import copy
 import os
 import sys
@@ -68,11 +69,12 @@ def _frame_map(m, q, qd, u, S):
 
 
 # the (step, seed) of the draw below that each (case, S) is compared at: the first that keeps the base's branches
-DRAW_USED = {("box_slide", 1): (1e-4, 0), ("box_slide", 2): (1e-4, 0), ("pusher", 1): (1e-4, 0), ("pusher", 2): (1e-4, 0)}
+DRAW_USED = {("box_slide", 1): (1e-4, 0), ("box_slide", 2): (1e-4, 0), ("pusher", 1): (1e-4, 0), ("pusher", 2): (1e-4, 0),
+             ("small:11", 1): (1e-4, 0), ("small:11", 2): (1e-4, 0), ("small:52", 1): (1e-4, 0), ("small:52", 2): (1e-4, 0)}
 
 
 @pytest.mark.parametrize("S", [1, 2])
-@pytest.mark.parametrize("name", ["box_slide", "pusher"])
+@pytest.mark.parametrize("name", ["box_slide", "pusher", "small:11", "small:52"])
 def test_oracle_frame_rows_are_the_derivative_of_its_one_frame_map(name, S):
     m, q0, qd0, u, S_case = tangent_case(name, 1)
     m = copy.deepcopy(m)
@@ -84,6 +86,10 @@ def test_oracle_frame_rows_are_the_derivative_of_its_one_frame_map(name, S):
     rows = oracle_frame_rows(m, q, qd, uf, S)
     x0, sig0, bad0 = _frame_map(m, q, qd, uf, S)
     assert bad0 == 0
+    if name.startswith("small:"):      # the builder on matrices whose elimination exchanges rows (tests/frame_jacobian_cases.py), before the GPU is held to it
+        import frame_jacobian_cases as FC
+        bad, Hs = FC.newton_matrices(m, q, qd, uf[None], S)
+        assert bad == 0 and all(FC.pivot_order(H)[0] != list(range(nr)) for H in Hs), name
     for h, seed in [(h_, s_) for h_ in (1e-4, 1e-5, 1e-6) for s_ in range(4)]:
         rng = np.random.default_rng(7 + seed)
         vq, vqd, vu = 0.01 * rng.normal(size=nr), 0.01 * rng.normal(size=nr), 0.1 * rng.normal(size=uf.shape)

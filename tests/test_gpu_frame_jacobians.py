@@ -12,7 +12,9 @@ of the whole episode against the scale the column test itself leaves open, propa
 builder, 1e-7 of the row's scale at Newton tol 1e-13 (the setting of tests/test_gpu_tangent.py's oracle test).
 The rest: the launch shapes, compiled-in model batches, exact zeros and the free-flight structure, that the launch changes nothing that exists, that
 the outputs are independent of each other and of the window, the refusals, the ragged batch, a captured launch.
-The refusal for a block that does not fit the LDS is not run: no model of the suite reaches it (a 16-dof, 16-motor fp64 block is 15 KB next to one context).
+The refusal for a block that does not fit the LDS is not run here: none of this file's models reaches it.  The 16-dof models of the random corpus do
+in fp64 (large:L2: a context of 59 KB and a column block of 12.6 KB at one environment per wavefront) — tests/test_gpu_frame_jacobian_edges.py runs it.
+The launch shape is held to tests/wide_models.py frame_jacobian_shape, the restated plan: lanes, LDS bytes and blocks, exactly.
 Cases: TANGENT_CASES without the two bdf2: ones (small:3 and large:L7 as BDF1 models: _case), B = 5 (ragged at 4 and 2 environments per wavefront), T = 3 frames of 2 sub-steps (pusher: 5)."""
 import copy
 import os
@@ -26,6 +28,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import tactilesimulation_amd.model.blob as Bl      # noqa: E402
 import param_grad_util as PU      # noqa: E402
+import wide_models as W      # noqa: E402
+from frame_jacobian_cases import ORACLE_CASES, as_bdf1 as _as_bdf1      # noqa: E402
 from test_tangent_yardstick import TANGENT_CASES, T_FRAMES, tangent_case      # noqa: E402
 from test_frame_jacobian_yardstick import oracle_frame_rows, oracle_frame_states      # noqa: E402
 
@@ -47,14 +51,6 @@ def _case(name, B):
     return _as_bdf1(*tangent_case(name, B))
 
 
-def _as_bdf1(m, q0, qd0, u, S):
-    if int(m.I[Bl.TSIM_IH_INTEGRATOR]) != 1:
-        m = copy.deepcopy(m)
-        m.I = np.array(m.I, copy=True)
-        m.I[Bl.TSIM_IH_INTEGRATOR] = 1
-    return m, q0, qd0, u, S
-
-
 def _t(x, dt):
     return torch.tensor(np.ascontiguousarray(x), device=DEV, dtype=dt)
 
@@ -67,15 +63,15 @@ def _roll(sim, tab, q0, qd0, u, S):
     return sim.rollout(_t(u.transpose(1, 0, 2), dt), S, want_qd=True)
 
 
-def _tangent_columns(sim, T, S, f):
+def _tangent_columns(sim, T, S, f, ndir=8):
     """([B, 2 nr, 2 nr + nu], dq [ncol, B, nr], dvar [ncol, B, nvar] or None) of frame f by k_tangent: the first output frame of a window over the
-    newest T - f frames, identity dq0 / dqd0 and a unit du on the window's first frame, eight directions per launch"""
+    newest T - f frames, identity dq0 / dqd0 and a unit du on the window's first frame, ndir (eight) directions per launch"""
     B, nr, nu, dt = sim.B, sim.ndof_r, sim.ndof_u, sim.dtype
     ncol, n = 2 * nr + nu, T - f
     M = torch.zeros((B, 2 * nr, ncol), device=DEV, dtype=dt)
     dqs, dvs = [], []
-    for c0 in range(0, ncol, 8):
-        cols = list(range(c0, min(c0 + 8, ncol)))
+    for c0 in range(0, ncol, ndir):
+        cols = list(range(c0, min(c0 + ndir, ncol)))
         dq0 = torch.zeros((len(cols), B, nr), device=DEV, dtype=dt)
         dqd0 = torch.zeros_like(dq0)
         du = torch.zeros((len(cols), n, B, nu), device=DEV, dtype=dt)
@@ -95,11 +91,16 @@ def _tangent_columns(sim, T, S, f):
     return M, torch.cat(dqs, 0), torch.cat(dvs, 0) if dvs else None
 
 
-def _column_errors(sim, T, S, fj):
+def _tangent_ndir(sim):
+    """directions per tangent_episode launch: eight, or the most (4, 2, 1) whose tangent state fits the block's LDS for this model"""
+    return next(nd for nd in (8, 4, 2, 1) if nd == 1 or sim.tangent_launch_info(nd, False)["lds_bytes"] <= 64 * 1024)
+
+
+def _column_errors(sim, T, S, fj, ndir=8):
     """(largest column error, largest Jvar error) over the frames, against k_tangent"""
     ecol, evar = 0.0, 0.0
     for f in range(T):
-        M, dq, dvar = _tangent_columns(sim, T, S, f)
+        M, dq, dvar = _tangent_columns(sim, T, S, f, ndir)
         AB = torch.cat([fj["A"][f], fj["B"][f]], 2).double()
         scale = AB.abs().amax(2, keepdim=True)
         assert float(scale.min()) > 0
@@ -114,7 +115,20 @@ def _column_errors(sim, T, S, fj):
     return ecol, evar
 
 
-def _check_columns(name, dtype, lanes=0, static=False, rows=True, expect_variant=None, case=None):
+def _assert_shape(sim, m, lanes, rows):
+    """k_frame_jacobian's launch is the restated plan's (tests/wide_models.py frame_jacobian_shape): lanes per environment, LDS bytes, blocks per
+    frame.  lanes: what the batch was forced to (0: nothing, or TSIM_LPE)"""
+    env = int(os.environ.get("TSIM_LPE", "0"))
+    forced = lanes or (env if env in (16, 32, 64) else 0)
+    n_simd = 4 * torch.cuda.get_device_properties(0).multi_processor_count
+    want = W.frame_jacobian_shape(m, forced, 8 if sim.dtype == F64 else 4, rows, sim.B, n_simd, sim.kernel_variant() != "generic")
+    fl = sim.frame_jacobians_launch_info()
+    assert (fl["lanes_per_env"], fl["lds_bytes"], fl["lds_bytes"] <= 64 * 1024) == want and fl["threads"] == 64, (forced, fl, want)
+    assert fl["blocks"] == -(-sim.B // (64 // fl["lanes_per_env"]))
+    return fl, want
+
+
+def _check_columns(name, dtype, lanes=0, static=False, rows=True, expect_variant=None, case=None, bound=None):
     B, T = 5, T_FRAMES
     m, q0, qd0, u, S = _as_bdf1(*case) if case else _case(name, B)
     sim = PU.make_sim(m, B, dtype, T * S, lanes=lanes, static=static)
@@ -122,22 +136,23 @@ def _check_columns(name, dtype, lanes=0, static=False, rows=True, expect_variant
     _roll(sim, tab, q0, qd0, u, S)
     if expect_variant:
         assert sim.kernel_variant() == expect_variant
-    bl, fl = sim.launch_info()["lanes_per_env"], sim.frame_jacobians_launch_info()
-    assert fl["lanes_per_env"] >= bl and fl["lds_bytes"] <= 64 * 1024 and fl["threads"] == 64, (bl, fl)
-    assert fl["blocks"] == -(-B // (64 // fl["lanes_per_env"]))
+    fl, _ = _assert_shape(sim, m, lanes, rows)
+    assert fl["lanes_per_env"] >= sim.launch_info()["lanes_per_env"] and fl["lds_bytes"] <= 64 * 1024, fl
     fj = sim.frame_jacobians(T, S, want_var=True)
     assert sim.tape_len() == T * S
     nr, nu = sim.ndof_r, sim.ndof_u
     assert tuple(fj["A"].shape) == (T, B, 2 * nr, 2 * nr) and tuple(fj["B"].shape) == (T, B, 2 * nr, nu)
     assert all(bool(torch.isfinite(x).all()) for x in fj.values())
-    ecol, evar = _column_errors(sim, T, S, fj)
+    ecol, evar = _column_errors(sim, T, S, fj, _tangent_ndir(sim))
     print("columns %-24s %s lanes %2d (k_frame_jacobian at %2d) static %d rows %d: column error %.3e Jvar error %.3e" % (
         name, "f64" if dtype == F64 else "f32", lanes, fl["lanes_per_env"], static, rows, ecol, evar))
     if STATS:
         with open(STATS, "a") as fh:
             fh.write("%s %s %d/%d %d %d %.4e %.4e\n" % (name, "f64" if dtype == F64 else "f32", lanes, fl["lanes_per_env"], static, rows, ecol, evar))
     assert MEASURED[dtype] < CAP[dtype]
-    assert ecol <= BOUND[dtype] and evar <= BOUND[dtype], (name, ecol, evar)
+    bound = bound or BOUND[dtype]      # (a case of tests/test_gpu_frame_jacobian_edges.py over BOUND: 10 x its own measured worst, which is under CAP)
+    assert BOUND[dtype] <= bound < 10 * CAP[dtype]
+    assert ecol <= bound and evar <= bound, (name, ecol, evar)
     return sim, fj
 
 
@@ -185,10 +200,12 @@ def test_chain_reproduces_the_episode_tangent(name, dtype):
 
 
 # ---------------------------------------------------------------------------------------------------- 3. against the oracle
-@pytest.mark.parametrize("name", ["pusher", "pad_press"])
+@pytest.mark.parametrize("name", ["pusher", "pad_press"] + ORACLE_CASES)
 def test_frame_jacobians_against_the_oracle_rows(name):
     """fp64, four environments with rows of their own, Newton tol 1e-13: every row of [A_f | B_f] against the oracle's adjoint rows of the frame
-    started at the oracle's own (q_f, qd_f), each entry within 1e-7 of the row's scale (its largest magnitude)"""
+    started at the oracle's own (q_f, qd_f), each entry within 1e-7 of the row's scale (its largest magnitude).  pusher and pad_press keep their
+    pivots on the diagonal; the corpus models of tests/frame_jacobian_cases.py ORACLE_CASES exchange rows, unambiguously, on these very rows
+    (tests/test_frame_jacobian_cases.py) — the one yardstick here that shares no taped H, K or point evaluation with k_tangent"""
     B, T = 4, T_FRAMES
     m, q0, qd0, u, S = _case(name, B)
     m = copy.deepcopy(m)
@@ -209,6 +226,9 @@ def test_frame_jacobians_against_the_oracle_rows(name):
             worst = max(worst, float(err.max()))
             assert np.all(err <= 1e-7), (name, e, f, float(err.max()))
     print("oracle rows %s: worst |entry - oracle| / row scale = %.3e" % (name, worst))
+    if STATS:
+        with open(STATS, "a") as fh:
+            fh.write("oracle_rows %s %.4e\n" % (name, worst))
 
 
 # ---------------------------------------------------------------------------------------------------- 4. launch shapes, compiled-in model batches
@@ -367,9 +387,10 @@ def test_refusals():
 
 # ---------------------------------------------------------------------------------------------------- 9. the ragged batch
 @pytest.mark.parametrize("dtype", [F64, F32])
-@pytest.mark.parametrize("name", ["pusher", "box_slide"])
+@pytest.mark.parametrize("name", ["pusher", "box_slide", "small:11"])
 def test_the_last_environment_of_a_ragged_batch(name, dtype):
-    """B = 5: environment 4 sits alone in the last block; its matrices are those of a B = 1 batch with its inputs, bit for bit"""
+    """B = 5: environment 4 sits alone in the last block; its matrices are those of a B = 1 batch with its inputs, bit for bit (small:11 of the
+    random corpus exchanges rows in its solve in every frame: tests/test_frame_jacobian_cases.py)"""
     B, T = 5, T_FRAMES
     m, q0, qd0, u, S = _case(name, B)
     rng = np.random.default_rng(5)

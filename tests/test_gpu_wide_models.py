@@ -338,15 +338,16 @@ def test_tangent_identity_with_the_contact_group_alone(name, dtype, lanes):
 
 # ---------------------------------------------------------------------------------------------------- 6. the census
 # An instantiation: (kernel, real "f" / "d", NRM — None where the kernel has no such parameter —, EXPJ, LPE).  REACHED_BY maps every generic
-# instantiation of the nine kernels to (case, forced lanes (0: the library's choice), per-environment rows, the test that runs it there); the
+# instantiation of the ten kernels to (case, forced lanes (0: the library's choice), per-environment rows, the test that runs it there); the
 # precision is the instantiation's.  Cases: the wide models (NRM 16 below 64 lanes, and at 64), "box_slide" (3 dofs: NRM 8, every shape in both
 # precisions) and "bdf2:tactile_pad" (a rotation-vector joint: EXPJ, 64 lanes whatever is asked for).  UNREACHABLE: the rest, with the arithmetic.
 # What ties an entry to its test: tests/test_wide_models.py reads the named test's parametrize marks and body for the case and the lanes, and the
 # plan test below asks the library for the shape of (case, lanes).  Neither executes the named test: a case it skipped at run time would not show.
-WITH_NRM = ("k_forward", "k_backward", "k_backward_z", "k_tangent", "k_tangent_src")
+WITH_NRM = ("k_forward", "k_backward", "k_backward_z", "k_tangent", "k_tangent_src", "k_frame_jacobian")
 WITHOUT_NRM = ("k_debug_eval", "k_param_grad", "k_param_grad_body", "k_tangent_body_src")
 _HERE = "test_gpu_wide_models.py::"
 _BODY = "test_gpu_body_param_grad_oracle.py::test_generic_body_gradient_against_the_oracle"
+_FJ = "test_gpu_frame_jacobians.py::"
 _TEST_OF = {      # kernel: the test that runs it on (the wide models, box_slide, bdf2:tactile_pad)
     "k_forward": (_HERE + "test_state_tactile_frame_and_adjoint_follow_the_oracle", _HERE + "test_three_dofs_follow_the_oracle_at_every_shape", _BODY),
     # (no table-gradient buffer: k_backward; with one: its twin k_backward_z, then the parameter passes)
@@ -362,8 +363,11 @@ _TEST_OF = {      # kernel: the test that runs it on (the wide models, box_slide
     "k_tangent_src": (_HERE + "test_tangent_identity_with_eight_directions", "test_gpu_tangent_body.py::test_identity_at_every_launch_shape",
                       "test_gpu_tangent_body.py::test_identity_with_body_directions"),
     "k_tangent_body_src": (_HERE + "test_tangent_identity_with_eight_directions", "test_gpu_tangent_body.py::test_identity_at_every_launch_shape",
-                           "test_gpu_tangent_body.py::test_identity_with_body_directions")}
-TANGENT_SHAPED = ("k_tangent", "k_tangent_src")      # their lanes are tsim_tangent_launch_info's; every other kernel runs at the batch's
+                           "test_gpu_tangent_body.py::test_identity_with_body_directions"),
+    # (BDF1 models only: its rotation-vector case is param_grad_util's "tactile_pad" run as a BDF1 model, not the BDF2 file's)
+    "k_frame_jacobian": (_FJ + "test_columns_on_the_wide_models", _FJ + "test_columns_at_every_launch_shape", _FJ + "test_columns_with_a_rotation_vector_joint")}
+TANGENT_SHAPED = ("k_tangent", "k_tangent_src")      # their lanes are tsim_tangent_launch_info's; every other kernel runs at the batch's ...
+FRAME_JACOBIAN_SHAPED = ("k_frame_jacobian",)        # ... but this one: tsim_frame_jacobians_launch_info's (wide_models.frame_jacobian_shape)
 
 
 def _census():
@@ -375,7 +379,8 @@ def _census():
         for r in "fd":
             for lpe in (16, 32, 64):
                 # more than 8 dofs at lpe lanes: wide10 forced to lpe — but k_tangent in fp32 at 16 lanes only wide9 (SHAPES), and nothing in fp64 at 16
-                wide = None if (r, lpe) == ("d", 16) else "wide9" if k in TANGENT_SHAPED and (r, lpe) == ("f", 16) else "wide10"
+                # (and k_frame_jacobian: four column blocks of wide10 next to four fp32 contexts exceed 64 KB too)
+                wide = None if (r, lpe) == ("d", 16) else "wide9" if k in TANGENT_SHAPED + FRAME_JACOBIAN_SHAPED and (r, lpe) == ("f", 16) else "wide10"
                 if k in WITH_NRM:
                     reached[k, r, 8, False, lpe] = ("box_slide", lpe, rows, t_box)
                     if wide:
@@ -385,7 +390,7 @@ def _census():
                 else:      # one instantiation for every number of dofs: the wide models where they reach the shape
                     reached[k, r, None, False, lpe] = (wide, lpe, rows, t_wide) if wide else ("box_slide", lpe, rows, t_box)
             if t_exp:
-                reached[k, r, 16 if k in WITH_NRM else None, True, 64] = ("bdf2:tactile_pad", 0, True, t_exp)
+                reached[k, r, 16 if k in WITH_NRM else None, True, 64] = ("tactile_pad" if k in FRAME_JACOBIAN_SHAPED else "bdf2:tactile_pad", 0, True, t_exp)
     return reached, unreachable
 
 
@@ -399,8 +404,8 @@ def census_model(case):
 @pytest.mark.parametrize("inst", sorted(REACHED_BY, key=str), ids=lambda i: "%s-%s-nrm%s-exp%d-lpe%d" % i)
 def test_the_plan_reaches_every_census_entry(inst):
     """the batch of the entry's case, created and forced as its test does, not simulated: the launch plan reports the entry's lanes per
-    environment (k_tangent, k_tangent_src: tsim_tangent_launch_info; the others: tsim_launch_info, the shape of the parameter passes and of the
-    pre-pass too) and the generic kernels, and the entry's NRM and EXPJ are the plan's rule for the model — NRM = 16 iff ndof_r > 8 or a
+    environment (k_tangent, k_tangent_src: tsim_tangent_launch_info; k_frame_jacobian: tsim_frame_jacobians_launch_info; the others:
+    tsim_launch_info, the shape of the parameter passes and of the pre-pass too) and the generic kernels, and the entry's NRM and EXPJ are the plan's rule for the model — NRM = 16 iff ndof_r > 8 or a
     rotation-vector joint (csrc/tsim_hip.hip ts_plan; the library reports no NRM, so the rule is restated here)"""
     kernel, r, nrm, expj, lpe = inst
     case, lanes, rows, test = REACHED_BY[inst]
@@ -409,7 +414,7 @@ def test_the_plan_reaches_every_census_entry(inst):
     sim = PU.make_sim(m, B, dtype, T * S, lanes=lanes)
     if rows:
         sim.set_env_tables(_t(PU.table_rows(m, B, dtype == F32, ROWS_SEED), dtype))
-    info = sim.tangent_launch_info(8, True) if kernel in TANGENT_SHAPED else sim.launch_info()
+    info = sim.tangent_launch_info(8, True) if kernel in TANGENT_SHAPED else sim.frame_jacobians_launch_info() if kernel in FRAME_JACOBIAN_SHAPED else sim.launch_info()
     assert info["lanes_per_env"] == lpe and info["lds_bytes"] <= W.LDS_CAP, (inst, REACHED_BY[inst], info)
     assert sim.kernel_variant() == "generic" and RC.has_exp_joint(m) == expj
     assert nrm is None or nrm == (16 if m.ndof_r > 8 or RC.has_exp_joint(m) else 8), (inst, m.ndof_r)

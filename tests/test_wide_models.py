@@ -206,13 +206,15 @@ def test_wide10_is_as_large_as_it_gets():
 # ---------------------------------------------------------------------------------------------------- the census
 def _generic_rows(table):
     """the generic non-policy instantiations of the kernel table: (kernel, real, NRM or None, EXPJ, LPE).  The patterns of
-    tests/test_capi_symbols.py for the four simulation kernels; the parameter passes and the tangent kernels have generic instantiations only"""
+    tests/test_capi_symbols.py for the four simulation kernels; the parameter passes, the tangent kernels and k_frame_jacobian have generic
+    instantiations only"""
     got = set()
     for name in table:
         m = re.match(r"_Z\d+(k_forward|k_backward|k_backward_z)I([fd])Li(\d+)ELb([01])ELi(\d+)ELb([01])E(.+?)Ev7[FB]wdArgs", name)
         d = re.match(r"_Z\d+k_debug_evalI([fd])Li(\d+)E(.+?)Ev7DbgArgs", name)
         p = re.match(r"_Z\d+(k_param_grad|k_param_grad_body|k_tangent_body_src)I([fd])Lb([01])ELi(\d+)EEv\d+(Pg|PgBody|TanBody)ArgsI", name)
-        t = re.match(r"_Z\d+(k_tangent|k_tangent_src)I([fd])Li(\d+)ELb([01])ELi(\d+)EEv7TanArgsI", name)
+        t = re.match(r"_Z\d+(k_tangent|k_tangent_src)I([fd])Li(\d+)ELb([01])ELi(\d+)EEv7TanArgsI", name) or \
+            re.match(r"_Z\d+(k_frame_jacobian)I([fd])Li(\d+)ELb([01])ELi(\d+)EEv6FjArgsI", name)
         if m and m[6] == "0" and m[7] == "v":
             got.add((m[1], m[2], int(m[3]), m[4] == "1", int(m[5])))
         elif d and d[3] == "v":
@@ -222,7 +224,7 @@ def _generic_rows(table):
         elif t:
             got.add((t[1], t[2], int(t[3]), t[4] == "1", int(t[5])))
         else:
-            assert not re.match(r"_Z\d+(k_param_grad|k_param_grad_body|k_tangent|k_tangent_src|k_tangent_body_src)I", name), name
+            assert not re.match(r"_Z\d+(k_param_grad|k_param_grad_body|k_tangent|k_tangent_src|k_tangent_body_src|k_frame_jacobian)I", name), name
     return got
 
 
@@ -258,7 +260,7 @@ def test_every_generic_instantiation_is_run_by_a_test_or_cannot_be():
         import __graft_entry__
         __graft_entry__.build()
     got = _generic_rows(json.load(open(buildhash.KERNELS_JSON)))
-    assert len(got) == 100 and not set(G.REACHED_BY) & set(G.UNREACHABLE)
+    assert len(got) == 114 and not set(G.REACHED_BY) & set(G.UNREACHABLE)
     assert set(G.REACHED_BY) | set(G.UNREACHABLE) == got, ("no test", sorted(got - set(G.REACHED_BY) - set(G.UNREACHABLE), key=str),
                                                              "no kernel", sorted((set(G.REACHED_BY) | set(G.UNREACHABLE)) - got, key=str))
     for inst in G.UNREACHABLE:
@@ -270,8 +272,9 @@ def test_every_generic_instantiation_is_run_by_a_test_or_cannot_be():
         assert (nrm is None or nrm == (16 if m.ndof_r > 8 or expj else 8)) and (not expj or lpe == 64), (kernel, r, nrm, expj, lpe)
         if not expj:
             esz = 8 if r == "d" else 4
-            shape = W.tangent_shape(m, lanes, esz, rows) if kernel in G.TANGENT_SHAPED else W.forced_shape(m, lanes, esz, rows)[0]
+            shape = W.tangent_shape(m, lanes, esz, rows) if kernel in G.TANGENT_SHAPED else \
+                W.frame_jacobian_shape(m, lanes, esz, rows)[0] if kernel in G.FRAME_JACOBIAN_SHAPED else W.forced_shape(m, lanes, esz, rows)[0]
             assert shape == lpe, (kernel, r, nrm, expj, lpe, case, lanes, shape)
         # NRM 16 below 64 lanes, and every row at 16 / 32 lanes that the wide models reach, is run by the new file
         if nrm == 16 and not expj:
-            assert case in W.WIDE and path == "test_gpu_wide_models.py"
+            assert case in W.WIDE and path == ("test_gpu_frame_jacobians.py" if kernel in G.FRAME_JACOBIAN_SHAPED else "test_gpu_wide_models.py")

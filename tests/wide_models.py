@@ -8,7 +8,9 @@ slides on the ground (a ground pair with general contact points, loaded and slip
 pair, taxels loaded), the finger sits beyond a limit (wide9: the upper, wide10: the lower one), and force and position motors drive the chain.
 
 The LDS arithmetic restates csrc/tsim_device.h (ts_lds_env_reals, ts_tab_reals, ts_lds_reals), csrc/tsim_tangent.h (ts_tan_slot_reals) and the size
-of the host's sweep schedule (csrc/tsim_hip.hip build_sched); the GPU file holds block_bytes() to what the library reports."""
+of the host's sweep schedule (csrc/tsim_hip.hip build_sched); the GPU file holds block_bytes() to what the library reports.  frame_jacobian_shape
+restates the launch plan of k_frame_jacobian (csrc/tsim_frame_jacobian.h ts_fj_slot_reals, csrc/tsim_hip.hip ts_plan / frame_jacobian_plan /
+launch_shape) for any model; tests/test_gpu_frame_jacobians.py and tests/test_gpu_frame_jacobian_edges.py hold it to the library."""
 import os
 import sys
 
@@ -139,6 +141,57 @@ def tangent_shape(m, lanes, esz, env_tables=True):
     while lanes < 64 and block_bytes(m, 64 // lanes, esz, env_tables, st) + (64 // lanes) * tangent_slot_bytes(m, esz) > LDS_CAP:
         lanes *= 2
     return lanes
+
+
+FJ_RHS = 8                          # csrc/tsim_frame_jacobian.h TS_FJ_RHS
+AUTO_LDS_CAP = 40 * 1024            # csrc/tsim_hip.hip launch_shape: the cap of a block where no shape is forced (room for four blocks per CU)
+
+
+def fj_slot_reals(nr, nu):
+    """csrc/tsim_frame_jacobian.h ts_fj_slot_reals: X [2 nr + nu][2 nr], MM [nr][nr], W [8][nr], DU [nu] of a slot, rounded up to four reals"""
+    return ((2 * nr + nu) * 2 * nr + nr * nr + FJ_RHS * nr + nu + 3) & ~3
+
+
+def _launch_lanes(m, lanes, esz, env_tables, st, B, n_simd, fused):
+    """csrc/tsim_hip.hip launch_shape for a batch of B environments: `lanes` forced, or (0) the shape of the fewest rounds x latency whose block
+    stays under 40 KB; 64 with a rotation-vector joint; then the lanes double until the block fits the cap"""
+    import random_corpus as RC
+    cap = LDS_CAP if lanes else AUTO_LDS_CAP
+    if not lanes:
+        lanes, best = 64, 1e30
+        lat = (1.0, 1.13, 1.24) if fused else (1.0, 0.93, 1.02)
+        for i, cand in enumerate((64, 32, 16)):
+            ns = 64 // cand
+            if i > 0 and block_bytes(m, ns, esz, env_tables, st) > cap:
+                break
+            t = -(-(-(-B // ns)) // n_simd) * lat[i]
+            if t < best:
+                best, lanes = t, cand
+    if RC.has_exp_joint(m):
+        lanes = 64
+    while lanes < 64 and block_bytes(m, 64 // lanes, esz, env_tables, st) > cap:
+        lanes *= 2
+    return lanes
+
+
+def frame_jacobian_shape(m, lanes, esz, env_tables=True, B=B_ENVS, n_simd=1024, fused=False):
+    """(lanes per environment, LDS bytes, fits) of k_frame_jacobian for a batch of B environments forced to `lanes` (0: the library's choice, which
+    depends on the device's SIMDs only for batches of more environments than it has SIMDs) — csrc/tsim_hip.hip ts_plan's TS_K_FRAME_JACOBIAN branch
+    and frame_jacobian_plan: the batch's shape (launch_shape, decide_stage_cpt; 64 lanes with a rotation-vector joint), then the lanes double until
+    the contexts and the slots' column blocks (fj_slot_reals) fit 64 KB; the blocks together are rounded up to 16 bytes.  fits: the launch is not
+    refused ("do not fit the block's LDS").  fused: the batch runs a compiled-in model's fused kernels (their latencies decide the automatic
+    shape)"""
+    st = False
+    if 3 * int(m.I[Bl.TSIM_IH_NCPT]) * esz <= CPT_LDS_BYTES:      # decide_stage_cpt
+        st = _launch_lanes(m, lanes, esz, env_tables, False, B, n_simd, fused) == _launch_lanes(m, lanes, esz, env_tables, True, B, n_simd, fused) \
+            and block_bytes(m, 1, esz, env_tables, True) <= LDS_CAP
+    lanes = _launch_lanes(m, lanes, esz, env_tables, st, B, n_simd, fused)
+    blk = fj_slot_reals(m.ndof_r, m.ndof_u) * esz
+    while lanes < 64 and block_bytes(m, 64 // lanes, esz, env_tables, st) + (64 // lanes) * blk > LDS_CAP:
+        lanes *= 2
+    ns = 64 // lanes
+    nbytes = block_bytes(m, ns, esz, env_tables, st) + (ns * blk + 15) // 16 * 16
+    return lanes, nbytes, nbytes <= LDS_CAP
 
 
 # ---------------------------------------------------------------------------------------------------- models and cases

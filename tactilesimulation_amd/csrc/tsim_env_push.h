@@ -81,8 +81,7 @@ extern "C" int tsim_push_action(int B, int dtype, const void* u, const void* ext
   TS_PUSH_ARGS_OK(B, dtype);
   if (!u || !ext || !action) return fail("tsim_push_action: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == TSIM_F32) hipLaunchKernelGGL(k_push_action<float>, dim3(push_blocks((long long)B * 6)), dim3(256), 0, st, B, (const float*)u, (const float*)ext, (float*)action);
-  else hipLaunchKernelGGL(k_push_action<double>, dim3(push_blocks((long long)B * 6)), dim3(256), 0, st, B, (const double*)u, (const double*)ext, (double*)action);
+  by_dtype(dtype, [&](auto r) { using R = decltype(r); hipLaunchKernelGGL(k_push_action<R>, dim3(push_blocks((long long)B * 6)), dim3(256), 0, st, B, (const R*)u, (const R*)ext, (R*)action); });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -91,8 +90,7 @@ extern "C" int tsim_push_action_backward(int B, int dtype, const void* u, const 
   TS_PUSH_ARGS_OK(B, dtype);
   if (!u || !d_action || !du) return fail("tsim_push_action_backward: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == TSIM_F32) hipLaunchKernelGGL(k_push_action_bwd<float>, dim3(push_blocks((long long)B * 3)), dim3(256), 0, st, B, (const float*)u, (const float*)d_action, (float*)du);
-  else hipLaunchKernelGGL(k_push_action_bwd<double>, dim3(push_blocks((long long)B * 3)), dim3(256), 0, st, B, (const double*)u, (const double*)d_action, (double*)du);
+  by_dtype(dtype, [&](auto r) { using R = decltype(r); hipLaunchKernelGGL(k_push_action_bwd<R>, dim3(push_blocks((long long)B * 3)), dim3(256), 0, st, B, (const R*)u, (const R*)d_action, (R*)du); });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -105,8 +103,10 @@ extern "C" int tsim_push_observe(int B, int ntac, int dtype, const void* q, cons
   if (rew && (!var || !u)) return fail("tsim_push_observe: the reward needs var and u");
   hipStream_t st = (hipStream_t)stream;
   const unsigned nb = push_blocks((long long)B * (3 + ntac));
-  if (dtype == TSIM_F32) hipLaunchKernelGGL(k_push_observe<float>, dim3(nb), dim3(256), 0, st, B, ntac, (const float*)q, (const float*)var, (const float*)tactile, (const float*)goal, (const float*)u, (float*)obs, (float*)rew);
-  else hipLaunchKernelGGL(k_push_observe<double>, dim3(nb), dim3(256), 0, st, B, ntac, (const double*)q, (const double*)var, (const double*)tactile, (const double*)goal, (const double*)u, (double*)obs, (double*)rew);
+  by_dtype(dtype, [&](auto r) {
+    using R = decltype(r);
+    hipLaunchKernelGGL(k_push_observe<R>, dim3(nb), dim3(256), 0, st, B, ntac, (const R*)q, (const R*)var, (const R*)tactile, (const R*)goal, (const R*)u, (R*)obs, (R*)rew);
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -120,8 +120,10 @@ extern "C" int tsim_push_observe_backward(int B, int ntac, int dtype, const void
   if (d_rew && (!var || !u || !dvar || !du)) return fail("tsim_push_observe_backward: the reward gradient needs var, u, dvar and du");
   hipStream_t st = (hipStream_t)stream;
   const unsigned nb = push_blocks((long long)B * (3 + ntac));
-  if (dtype == TSIM_F32) hipLaunchKernelGGL(k_push_observe_bwd<float>, dim3(nb), dim3(256), 0, st, B, ntac, (const float*)q, (const float*)var, (const float*)goal, (const float*)u, (const float*)d_obs, (const float*)d_rew, d_rew_stride, (float*)dq, (float*)dvar, (float*)dtac, (float*)du);
-  else hipLaunchKernelGGL(k_push_observe_bwd<double>, dim3(nb), dim3(256), 0, st, B, ntac, (const double*)q, (const double*)var, (const double*)goal, (const double*)u, (const double*)d_obs, (const double*)d_rew, d_rew_stride, (double*)dq, (double*)dvar, (double*)dtac, (double*)du);
+  by_dtype(dtype, [&](auto r) {
+    using R = decltype(r);
+    hipLaunchKernelGGL(k_push_observe_bwd<R>, dim3(nb), dim3(256), 0, st, B, ntac, (const R*)q, (const R*)var, (const R*)goal, (const R*)u, (const R*)d_obs, (const R*)d_rew, d_rew_stride, (R*)dq, (R*)dvar, (R*)dtac, (R*)du);
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -143,7 +145,7 @@ static PushPolicy<R> make_push_policy(const tsim_push_policy* p) {
 static int push_closed_check(const tsim_batch* b, const tsim_push_policy* pol, int num_frames, int num_steps, const char* who) {
   if (!b || !pol) return fail(std::string(who) + ": null batch / policy");
   if (b->nr != 7 || b->nu != 6 || 3 * b->ntax != PP_NTAC || b->nvar != 2 || b->has_exp) return fail(std::string(who) + ": not the TactilePush model (ndof_r 7, ndof_u 6, 130 taxels, 2 end-effector points)");
-  if (num_frames <= 0 || num_steps <= 0) return fail(std::string(who) + ": num_frames and num_steps must be positive");
+  if (int rc = frames_positive(who, num_frames, num_steps)) return rc;
   if (TS_PAIR_GROUP * ((int)PP_SIZE + b->nr * (int)PT_SIZE) < 64 * (int)PP_OCH + 2 * (int)PP_HID) return fail(std::string(who) + ": the pair-staging records are too small for the policy scratch");
   if (!pol->W1T || !pol->b1 || !pol->W2T || !pol->b2 || !pol->W3 || !pol->b3) return fail(std::string(who) + ": policy weights missing");
   if (push_obs_len(pol->obs_mode) < 0) return fail(std::string(who) + ": obs_mode must be 0 (tactile_flatten), 1 (no_tactile) or 2 (privilege)");
@@ -177,9 +179,7 @@ extern "C" int tsim_push_closed_rollout(tsim_batch* b, const tsim_push_policy* p
   if (pol->obs_mode == TSIM_PUSH_OBS_TACTILE && (!tac0 || !tac_out)) return fail("push_closed_rollout: tac0 and tac_out are required with the tactile observation (they feed it)");
   if (b->record && b->t_cur + (long long)num_frames * num_steps > b->cap) return fail("push_closed_rollout: tape capacity exceeded (" + std::to_string(b->cap) + " sub-steps)");
   TS_DEVICE(b);
-  int rc = b->dtype == TSIM_F32 ? push_closed_rollout_t<float>(b, pol, goal, dist, tac0, num_frames, num_steps, q_out, qd_out, var_out, tac_out, u_out, gl_out, h1_out, h2_out, status, (hipStream_t)stream)
-                                : push_closed_rollout_t<double>(b, pol, goal, dist, tac0, num_frames, num_steps, q_out, qd_out, var_out, tac_out, u_out, gl_out, h1_out, h2_out, status, (hipStream_t)stream);
-  if (rc) return rc;
+  if (int rc = by_real(b, [&](auto r) { return push_closed_rollout_t<decltype(r)>(b, pol, goal, dist, tac0, num_frames, num_steps, q_out, qd_out, var_out, tac_out, u_out, gl_out, h1_out, h2_out, status, (hipStream_t)stream); })) return rc;
   if (b->record) b->t_cur += num_frames * num_steps;
   b->has_prev = 1;
   return 0;
@@ -212,7 +212,7 @@ static int push_closed_backward_t(tsim_batch* b, const tsim_push_policy* pol, co
     HIPCHK(hipGetLastError());
     seeds = (const R*)dobs_tac + (size_t)b->B * PP_NTAC;
   }
-  return launch_param_passes<R>(b, a.n, nsub, 1, seeds ? b->pg_slots : nullptr, seeds, st);
+  return launch_param_passes<R>(b, a.n, nsub, 1, seeds ? (const int32_t*)b->pg_slots : nullptr, seeds, st);
 }
 
 extern "C" int tsim_push_closed_backward(tsim_batch* b, const tsim_push_policy* pol, const void* goal, int num_frames, int num_steps,
@@ -221,14 +221,12 @@ extern "C" int tsim_push_closed_backward(tsim_batch* b, const tsim_push_policy* 
   if (int rc = push_closed_check(b, pol, num_frames, num_steps, "push_closed_backward")) return rc;
   if (!pol->W1p || !pol->W2 || pol->w1_stride < push_obs_len(pol->obs_mode) || pol->w1_stride % 4 || pol->w1_stride > 64 * (int)PP_OCH) return fail("push_closed_backward: W1p [64][w1_stride >= observation length, multiple of 4] and W2 are required");
   if (!b->record) return fail("push_closed_backward: reset(backward_flag=True) was not called");
-  const long long n = (long long)num_frames * num_steps;
-  if (n > b->t_cur) return fail("push_closed_backward: only " + std::to_string(b->t_cur) + " sub-steps on the tape");
+  long long n;
+  if (int rc = taped_window(b, "push_closed_backward", num_frames, num_steps, &n)) return rc;
   if (!goal || !du_direct || !u_out || !h1_out || !h2_out || !g1_out || !g2_out || !g3_out) return fail("push_closed_backward: null pointer");
   if (pol->obs_mode == TSIM_PUSH_OBS_TACTILE && !dobs_tac) return fail("push_closed_backward: dobs_tac is required with the tactile observation");
   TS_DEVICE(b);
-  int rc = b->dtype == TSIM_F32 ? push_closed_backward_t<float>(b, pol, goal, num_frames, num_steps, df_dq, df_dvar, du_direct, u_out, h1_out, h2_out, g1_out, g2_out, g3_out, dobs_tac, df_du, (hipStream_t)stream)
-                                : push_closed_backward_t<double>(b, pol, goal, num_frames, num_steps, df_dq, df_dvar, du_direct, u_out, h1_out, h2_out, g1_out, g2_out, g3_out, dobs_tac, df_du, (hipStream_t)stream);
-  if (rc) return rc;
+  if (int rc = by_real(b, [&](auto r) { return push_closed_backward_t<decltype(r)>(b, pol, goal, num_frames, num_steps, df_dq, df_dvar, du_direct, u_out, h1_out, h2_out, g1_out, g2_out, g3_out, dobs_tac, df_du, (hipStream_t)stream); })) return rc;
   b->t_cur -= (int)n;
   pose_invalidate(b, (hipStream_t)stream);
   return 0;
@@ -246,8 +244,7 @@ static int push_closed_tangent_t(tsim_batch* b, const tsim_push_policy* pol, con
   a.pol.goal = (const R*)goal; a.pol.u_out = (R*)u_out; a.pol.h1_out = (R*)h1_out; a.pol.h2_out = (R*)h2_out;      // (read only here)
   a.s1 = (const R*)s1; a.s2 = (const R*)s2; a.s3 = (const R*)s3; a.dact = (const R*)dact; a.dtac0 = (const R*)dtac0;
   a.dupol_out = (R*)dupol_out; a.du_out = (R*)du_out;
-  size_t ctx_lds;
-  const TsPlan plan = tangent_plan(b, ndir, dtab != nullptr, &ctx_lds, TS_K_CLOSED_TANGENT);
+  const auto [plan, ctx_lds] = tangent_plan(b, ndir, dtab != nullptr, TS_K_CLOSED_TANGENT);
   a.xoff = (int)(ctx_lds / b->esz);
   if (plan.lds > TS_TAN_LDS_CAP) return fail("push_closed_tangent: the tangent state of " + std::to_string(ndir) + " directions does not fit the block's LDS");
   if (int rc = launch_tangent_body_src<R>(b, a, st, "push_closed_tangent")) return rc;      // body groups on and dtables given: k_tangent_body_src first, unchanged
@@ -267,20 +264,15 @@ extern "C" int tsim_push_closed_tangent(tsim_batch* b, const tsim_push_policy* p
   if (!b->record || b->t_cur <= 0) return fail("push_closed_tangent: no tape recorded (reset(backward_flag=True), then tsim_push_closed_rollout)");
   const long long n = (long long)num_frames * num_steps;
   if (n > b->t_cur) return fail("push_closed_tangent: the window is the newest num_frames x num_steps = " + std::to_string(n) + " taped sub-steps, the tape holds only " + std::to_string(b->t_cur));
-  if (b->I[TSIM_IH_INTEGRATOR] == 2 && n != b->t_cur)
-    return fail("push_closed_tangent: a BDF2 model's window must start at tape record 0 (no tangent is carried across calls); the tape holds " + std::to_string(b->t_cur) + " sub-steps");
+  if (int rc = bdf2_window_is_the_tape(b, "push_closed_tangent", n)) return rc;
   if (!goal || !u_out || !h1_out || !h2_out) return fail("push_closed_tangent: null pointer (goal and the forward records u, h1, h2 are required)");
   if (pol->obs_mode == TSIM_PUSH_OBS_TACTILE && !dtac_out) return fail("push_closed_tangent: dtac_out is required with the tactile observation (workspace and result: frame f observes row f - 1)");
   TS_DEVICE(b);
-  return b->dtype == TSIM_F32 ? push_closed_tangent_t<float>(b, pol, goal, num_frames, num_steps, ndir, u_out, h1_out, h2_out, s1, s2, s3, dact, dtac0, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, dupol_out, du_out, (hipStream_t)stream)
-                              : push_closed_tangent_t<double>(b, pol, goal, num_frames, num_steps, ndir, u_out, h1_out, h2_out, s1, s2, s3, dact, dtac0, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, dupol_out, du_out, (hipStream_t)stream);
+  return by_real(b, [&](auto r) { return push_closed_tangent_t<decltype(r)>(b, pol, goal, num_frames, num_steps, ndir, u_out, h1_out, h2_out, s1, s2, s3, dact, dtac0, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, dupol_out, du_out, (hipStream_t)stream); });
 }
 
 extern "C" int tsim_push_closed_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, int32_t* out) {
   if (!b || !out) return fail("push_closed_tangent_launch_info: null argument");
   if (ndir < 1 || ndir > TSIM_TANGENT_MAX_DIR) return fail("push_closed_tangent_launch_info: ndir must be 1 .. " + std::to_string((int)TSIM_TANGENT_MAX_DIR));
-  size_t ctx_lds;
-  const TsPlan p = tangent_plan(b, ndir, with_dtables != 0, &ctx_lds, TS_K_CLOSED_TANGENT);
-  out[0] = (int32_t)p.lds; out[1] = TS_WAVE; out[2] = (int32_t)p.grid; out[3] = p.lpe;
-  return 0;
+  return plan_info(tangent_plan(b, ndir, with_dtables != 0, TS_K_CLOSED_TANGENT).plan, out);
 }

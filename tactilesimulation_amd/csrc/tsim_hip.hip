@@ -27,6 +27,7 @@
 #include "tsim_kernels.h"
 #include "tsim_param_grad.h"
 #include "tsim_launch.h"
+#include "tsim_batch.h"      // the batch, the error text, the device guard, the precision dispatch, the owned buffers (host only)
 
 // ================================================================================================ LPT ordering
 // One block: counting sort of the environments by their residual-evaluation count of the last launch, descending
@@ -391,118 +392,12 @@ __global__ void __launch_bounds__(TS_WAVE) k_signature(SigArgs<R> a) {
 }
 
 // ================================================================================================ host side
-static thread_local std::string g_err;
-static int fail(const std::string& m) { g_err = m; return 1; }
 int tsim_fail_(const std::string& m) { return fail(m); }      // for the library's other translation units (tsim_model.cpp)
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
-// Every entry point runs on the batch's device and leaves the calling thread's current device as it found it (a process
-// may drive several GPUs, and torch's current device / current_stream() follow the thread's HIP device).
-struct DeviceGuard {
-  int prev = -1; bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess; else prev = -1;
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#define TS_DEVICE(b) DeviceGuard guard_((b)->device); if (!guard_.ok) return fail("hipSetDevice(" + std::to_string((b)->device) + ") failed")
-
-struct CacheEntry { void* buf; int len; int record, tape_k_ok; };
-struct KtPair { hipEvent_t a, b; int kind; };
-struct tsim_batch {
-  int B, dtype, device, cap;
-  std::vector<int32_t> I; std::vector<double> F;
-  int nl, nr, nu, nvar, ntax, rec;
-  // The tape records of a batch created with a compiled-in model (kernel_mode: the fused static instantiations) hold K next to H (ts_rec: tape_k).
-  // tape_k_ok: every record since the last reset was written by such an instantiation, which the fused adjoint kernels need (launch_backward)
-  int tape_k = 0, tape_k_ok = 0;
-  int* dI; void* dF;             // model on device (dF in the batch's real type)
-  void* dFenv; int nfrec;        // optional per-environment float tables [B][nfrec] (domain randomisation)
-  void* tape;                    // [(cap+1)][B][rec]
-  void *lamq, *lamv;             // carried adjoint [2][B][nr]: of the state the next adjoint sub-step starts from, and (BDF2) what later
-                                 // sub-steps already contributed to the state one step further back
-  int* evals;                    // residual evaluations of the last forward launch, per env
-  int* helped = nullptr;         // ... and how many of its line-search trials a helper slot evaluated (k_forward; tsim_last_helper_trials)
-  float* gnorm = nullptr;        // largest ||g|| a sub-step of the last forward launch ended with, per env
-  int cross_kinks = 0, eval_budget = 0;     // tsim_set_solver_options
-  int* order; int order_valid;   // block -> env map for the next forward launch (LPT scheduling)
-  int* order_ep = nullptr; int order_ep_n = 0;   // ... for the next EPISODE launch of order_ep_n sub-steps (from the previous one's totals; survives reset)
-  void* prev; int has_prev;      // BDF2: state before the previous sub-step [B][2 nr]
-  void* poseR; double* poseD; int nspt;   // tsim_readout: pose records [B][nspt] of the (sensor, primitive) combinations (k_readout -> k_taxels)
-  int has_exp;                   // model contains a rotation-vector joint
-  int t_cur, record;
-  int lpe_forced;                // lanes per environment forced by TSIM_LPE (0 = choose from the batch size)
-  int nsched;                    // ints of the sweep schedule appended to dI
-  int stage_cpt;                 // the contact-point arrays are staged in LDS with the shared tables
-  int n_simd;                    // SIMDs of the device (CUs x 4)
-  int last_frame_rec = 0;        // the newest forward launch left its frames' outputs to k_frame_records (1; 2: and ran k_forward_fr; tsim_get_option TSIM_OPT_FRAME_RECORDS)
-  int value_trials = 2;          // line-search trials after this many rejected ones evaluate the residual only (0: off; tsim_set_option TSIM_OPT_VALUE_TRIALS; TSIM_VALUE_TRIALS=n at creation)
-  int trial_helpers = 1;        // finished slots of a wavefront evaluate the next line-search trials of a slot that is still in one (tsim_set_option TSIM_OPT_TRIAL_HELPERS; TSIM_NO_TRIAL_HELPERS=1 at creation: off)
-  int value_first = 1;           // launches without a tape: the first trial after a Newton step evaluates the residual only where the previous sub-step converged in one step (tsim_set_option TSIM_OPT_VALUE_FIRST; TSIM_NO_VALUE_FIRST=1 at creation: off)
-  // A/B switches of the environment, read ONCE at creation (launches are on the host-bound path of the per-step collectors):
-  // TSIM_NO_EPISODE_LPT, TSIM_INKERNEL_READOUT, TSIM_NO_FREE_RUN, TSIM_LOCKSTEP, TSIM_TAXELS_PER_RECORD, TSIM_NO_ENVTAB_CPT
-  bool ab_no_episode_lpt = false, ab_inkernel_readout = false, ab_no_free_run = false, ab_lockstep = false, ab_taxels_per_record = false, ab_no_envtab_cpt = false, ab_no_default_opts = false, ab_inkernel_frame_out = false; int ab_bwd_lpe = 0, ab_lpt_deal = 2;
-  int pair_cull = 1;             // phase 2 skips contact pairs out of reach of their primitive (tsim_set_option TSIM_OPT_PAIR_CULL; TSIM_NO_PAIR_CULL=1 at creation: off)
-  // Compiled-in models (csrc/tsim_static.h).  static_id: the model whose STRUCTURE the batch's blob has (ints + the structural floats: 1 TactilePush);
-  // static_exact: every float record equals the compiled asset's bit for bit as well (the fully static instantiation); env_struct_ok: the
-  // per-environment tables keep the structural floats (checked on the device by tsim_set_env_tables).  TSIM_NO_STATIC=1 at creation /
-  // tsim_set_static(0) keep the generic kernels.
-  int static_id = 0, static_exact = 0, env_struct_ok = 0, no_static = 0;
-  unsigned char* dKmask = nullptr; int* dFlag = nullptr;      // structural-float mask of static_id on the device, one-int result of the table check
-  void* fposeR = nullptr; double* fposeD = nullptr; int fpose_frames = 0;   // pose records per frame [fpose_frames][B][nspt] of episode launches with a deferred read-out
-  int pose_valid = 0;            // the pose records are those of the current state (left by the last forward launch)
-  int pose_off = 0;              // a launch of this batch was captured in a HIP graph: replays change the state behind the host's back, no reuse
-  int tt_off = 0;                // offset of the taxel staging table in the device int blob (I[NI] + S[TS_SCHED_TAXTAB])
-  int tax_slots = 0;             // blocks of k_taxels the device holds at once (occupancy x CUs), queried on first use
-  size_t esz;
-  std::vector<CacheEntry> cache;   // saved tapes, newest last
-  std::vector<void*> pool;          // spare tape buffers
-  std::vector<void*> retired;       // per-frame pose records (launch_forward) and tangent workspaces (launch_tangent) replaced by larger ones while a captured graph may still name them
-  long long* bwd_stamps = nullptr;  // diagnostics (tsim_debug_stamps)
-  // tsim_set_param_grad: the caller's table gradient [B][nfrec] (null: off), the adjoint solutions z [cap][B][nr] the adjoint launch saves for the
-  // parameter passes, and the contact pass's partial sums [pg_chunks][B][ts_pg_count] (pg_alloc: both when the gradient is first asked for)
-  void* dLdp = nullptr; void* zbuf = nullptr; void* pgpart = nullptr; int pg_chunks = 0;
-  // tsim_set_param_grad_groups: which groups of columns a launch adds to (TSIM_PG_*), and the body pass's partial sums
-  // [pg_chunks][B][ts_pgb_count] (pg_alloc: once a body group is on and the gradient is asked for)
-  int pg_groups = TS_PG_CONTACT; void* pgbpart = nullptr;
-  // tsim_tangent_episode with a body group on: the body columns' part of every sub-step's source, [ndir][n][B][nr] (k_tangent_body_src writes it,
-  // k_tangent reads it).  Grows only: allocated by the first call that needs it or needs it larger (launch_tangent), tan_src_reals its size
-  // tan_src_captured: a launch that names the current workspace was issued under stream capture, so growth retires it instead of freeing it
-  void* tan_src = nullptr; size_t tan_src_reals = 0; int tan_src_captured = 0;
-  // the closed-loop adjoint with the buffer set (tsim_push_closed_backward): frame -> seed row of the contact pass, [cap] (pg_alloc; written on the
-  // launch's stream by ts_closed_slots_launch)
-  int32_t* pg_slots = nullptr;
-  // diagnostics (tsim_last_adjoint_launch): the kernel of the most recent adjoint launch (TSIM_ADJ_*, -1: none yet) and the parameter passes behind it
-  int adj_kernel = -1, adj_passes = 0;
-  // tsim_kernel_timing: HIP events around every launch of the simulation kernels, on the stream they are launched on
-  int kt_on = 0;
-  std::vector<KtPair> kt;           // pairs recorded since the last tsim_kernel_times
-  std::vector<hipEvent_t> kt_free;  // events to reuse
-};
-// One timed launch: start event in the constructor, stop event in the destructor (nothing under stream capture: no events inside a graph).
-struct KtScope {
-  tsim_batch* b; hipStream_t st; KtPair p; bool on = false;
-  KtScope(tsim_batch* b_, int kind, hipStream_t st_) : b(b_), st(st_) {
-    if (!b->kt_on || b->kt.size() >= (size_t)1 << 16) return;      // (a caller that never reads the times back does not grow the list without bound)
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return;
-    hipEvent_t e[2];
-    for (int i = 0; i < 2; ++i) {
-      if (!b->kt_free.empty()) { e[i] = b->kt_free.back(); b->kt_free.pop_back(); }
-      else if (hipEventCreate(&e[i]) != hipSuccess) { (void)hipGetLastError(); if (i) b->kt_free.push_back(e[0]); return; }
-    }
-    p.a = e[0]; p.b = e[1]; p.kind = kind;
-    on = hipEventRecord(p.a, st) == hipSuccess;
-    if (!on) { b->kt_free.push_back(e[0]); b->kt_free.push_back(e[1]); }
-  }
-  ~KtScope() { if (on) { (void)hipEventRecord(p.b, st); b->kt.push_back(p); } }
-};
 // The state changed other than by a forward launch (or is about to, in a captured graph): tsim_readout recomputes the kinematics.
 static void pose_invalidate(tsim_batch* b, hipStream_t st) {
   b->pose_valid = 0;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) b->pose_off = 1;
+  if (capturing(st)) b->pose_off = 1;
 }
 
 
@@ -655,18 +550,15 @@ static int upload_model(tsim_batch* b, hipStream_t st) {
     std::vector<int32_t> S = build_sched(b->I, b->F);              // appended to the device copy at I[TSIM_IH_NI]
     if ((int)S.size() != b->nsched) return fail("sweep schedule size changed");
     b->tt_off = b->I[TSIM_IH_NI] + S[TS_SCHED_TAXTAB];
-    HIPCHK(hipMemcpyAsync(b->dI + b->I.size(), S.data(), S.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((int32_t*)b->dI + b->I.size(), S.data(), S.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  if (b->dtype == TSIM_F32) {
-    std::vector<float> f(b->F.begin(), b->F.end());
-    HIPCHK(hipMemcpyAsync(b->dF, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  return by_real(b, [&](auto r) {
+    const std::vector<decltype(r)> f(b->F.begin(), b->F.end());      // the float records in the batch's real type
+    HIPCHK(hipMemcpyAsync(b->dF, f.data(), f.size() * sizeof(r), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));   // f is a temporary
-  } else {
-    HIPCHK(hipMemcpyAsync(b->dF, b->F.data(), b->F.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // Zero-fill by a plain kernel.  hipMemsetAsync nodes did NOT reliably take effect when a captured HIP graph was replayed
@@ -725,7 +617,7 @@ template <class R> __global__ void k_get_state(const R* tape_rec, R* q, R* qd, i
 
 // dynamic LDS of a block of nslot environments
 static size_t lds_bytes_for(const tsim_batch* b, int nslot) {
-  const int reals = ts_lds_reals(b->nl, b->nr, b->nu, b->nfrec, b->I[TSIM_IH_NCPT], b->stage_cpt != 0, nslot, b->dFenv != nullptr, b->nsched + (int)b->I.size(), (int)b->esz);
+  const int reals = ts_lds_reals(b->nl, b->nr, b->nu, b->nfrec, b->I[TSIM_IH_NCPT], b->stage_cpt != 0, nslot, bool(b->dFenv), b->nsched + (int)b->I.size(), (int)b->esz);
   return ((size_t)reals * b->esz + 15) / 16 * 16;
 }
 // Launch shape of the forward / backward kernels.
@@ -777,12 +669,32 @@ static void decide_stage_cpt(tsim_batch* b) {
   b->stage_cpt = 1;
   if (launch_shape(b, b->lpe_forced).lpe != lpe0 || lds_bytes_for(b, 1) > 64 * 1024) b->stage_cpt = 0;
 }
+// What the launch shape depends on may have changed (forced lanes, the view, the model, per-environment tables): the block orders of the last
+// launches are for another shape, and the staging is decided again (the flag travels with every launch as a kernel argument: nothing on the device to update)
+static void shape_changed(tsim_batch* b) {
+  b->order_valid = 0; b->order_ep_n = 0;
+  decide_stage_cpt(b);
+}
 // ================================================================================================ launch plan
 // Which instantiation of a simulation kernel a launch runs, at which shape — decided here and nowhere else (tsim_launch.h launches the plan).
 // kernel: TS_K_*; policy: the closed loop; lpe: lanes per environment asked for by this launch (0: the batch's, TSIM_LPE /
 // tsim_set_lanes_per_env); the precision is the batch's.  The view is the batch's (kernel_mode) — for the adjoint kernels only on a tape whose
 // K the forward wrote (tape_k_ok: the fused adjoint reads it) — where it has an instantiation (ts_instantiated), else the generic kernels.
 enum { TS_TAN_LDS_CAP = 64 * 1024 };      // dynamic LDS of a k_tangent block
+// A launch whose every slot holds a block of reals behind the contexts (the tangent passes, the frame Jacobians).  shape_reals: the block the
+// SHAPE is chosen for — where the contexts and the slots' blocks are over the cap, fewer environments share a wavefront.
+// 0 is for a plan that ts_plan has shaped already (tangent_plan, frame_jacobian_plan): that plan's contexts fit the cap or its lanes are all 64, so
+// the loop below leaves them and the grid comes out as ts_plan's.  own_reals: the block of this launch.  The plan's grid is that of the shape, its LDS the contexts' (ctx_lds: where the blocks begin) and the
+// launch's own blocks behind them
+struct SlotPlan { TsPlan plan; size_t ctx_lds; };
+static SlotPlan slot_block_plan(const tsim_batch* b, TsPlan p, int shape_reals, int own_reals) {
+  while (p.lpe < TS_WAVE && lds_bytes_for(b, TS_WAVE / p.lpe) + (TS_WAVE / p.lpe) * ((size_t)shape_reals * b->esz) > TS_TAN_LDS_CAP) p.lpe *= 2;
+  const int ns = TS_WAVE / p.lpe;
+  p.grid = (unsigned)((b->B + ns - 1) / ns);
+  const size_t ctx_lds = lds_bytes_for(b, ns);
+  p.lds = ctx_lds + (((size_t)ns * own_reals * b->esz + 15) / 16) * 16;
+  return {p, ctx_lds};
+}
 static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   int forced = lpe ? lpe : b->lpe_forced;
   if (kernel == TS_K_DEBUG_EVAL && !forced) forced = TS_WAVE;      // the debug kernel: one environment per wavefront unless a shape is forced
@@ -800,22 +712,12 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
     // directions with parameters, whatever the launch asks for — the shape must not depend on ndir or on which inputs are given —: where the
     // block's LDS does not hold that, fewer environments share a wavefront.  grid and lds are those of the contexts; launch_tangent adds the
     // launch's own tangent blocks
-    const size_t most = (size_t)ts_tan_slot_reals(b->nr, b->nu, ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr), 4, TS_TAN_MAX_DIR) * b->esz;
-    while (p.lpe < TS_WAVE && lds_bytes_for(b, TS_WAVE / p.lpe) + (TS_WAVE / p.lpe) * most > TS_TAN_LDS_CAP) p.lpe *= 2;
-    const int ns = TS_WAVE / p.lpe;
-    p.grid = (unsigned)((b->B + ns - 1) / ns);
-    p.lds = lds_bytes_for(b, ns);
+    return slot_block_plan(b, p, ts_tan_slot_reals(b->nr, b->nu, ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr), 4, TS_TAN_MAX_DIR), 0).plan;
   }
-  if (kernel == TS_K_FRAME_JACOBIAN) {
-    // the frame Jacobians: every slot holds its 2 nr + nu columns behind the contexts (tsim_frame_jacobian.h), whichever outputs are asked for; where
-    // the block's LDS does not hold that, fewer environments share a wavefront.  lds is the contexts'; frame_jacobian_plan adds the blocks and
-    // multiplies the grid by the frames
-    const size_t blk = (size_t)ts_fj_slot_reals(b->nr, b->nu) * b->esz;
-    while (p.lpe < TS_WAVE && lds_bytes_for(b, TS_WAVE / p.lpe) + (TS_WAVE / p.lpe) * blk > TS_TAN_LDS_CAP) p.lpe *= 2;
-    const int ns = TS_WAVE / p.lpe;
-    p.grid = (unsigned)((b->B + ns - 1) / ns);
-    p.lds = lds_bytes_for(b, ns);
-  }
+  // the frame Jacobians: every slot holds its 2 nr + nu columns behind the contexts (tsim_frame_jacobian.h), whichever outputs are asked for; where
+  // the block's LDS does not hold that, fewer environments share a wavefront.  lds is the contexts'; frame_jacobian_plan adds the blocks,
+  // launch_frame_jacobians multiplies the grid by the frames
+  if (kernel == TS_K_FRAME_JACOBIAN) return slot_block_plan(b, p, ts_fj_slot_reals(b->nr, b->nu), 0).plan;
   return p;
 }
 // the kernel arguments that come from the batch; each launch sets its own
@@ -880,7 +782,7 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   FwdArgs<R> a = fwd_args<R>(b);
   a.nsub = nsub; a.nframes = nframes; a.tac_slot = tac_slot; a.u = (const R*)u;
   a.q_out = (R*)q_out; a.qd_out = (R*)qd_out; a.var_out = (R*)var_out; a.tac_out = (R*)tac_out; a.status = status;
-  a.order = (b->B >= 256 && nframes == 1 && b->order_valid) ? b->order : (b->B >= 256 && nframes > 1 && b->order_ep_n == nframes * nsub && !b->ab_no_episode_lpt) ? b->order_ep : nullptr;
+  a.order = (b->B >= 256 && nframes == 1 && b->order_valid) ? (const int*)b->order : (b->B >= 256 && nframes > 1 && b->order_ep_n == nframes * nsub && !b->ab_no_episode_lpt) ? (const int*)b->order_ep : nullptr;
   a.vo_first = b->value_first; a.helpers = b->trial_helpers; a.helped = b->helped;
   const bool emit = pose_emit(b, st);
   a.nspt = b->nspt;
@@ -892,19 +794,14 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   const size_t fpose_bytes = (size_t)nframes * b->B * (size_t)std::max(b->nspt, 1) * (TP_R_SIZE * b->esz + TP_D_SIZE * sizeof(double));
   bool defer = tac_out && taxels_supported(b) && fpose_bytes <= ((size_t)1 << 30) && !b->ab_inkernel_readout;
   if (defer && b->fpose_frames < nframes) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) defer = false;      // no allocation inside a capture: the in-kernel read-out
+    if (capturing(st)) defer = false;      // no allocation inside a capture: the in-kernel read-out
     else {
-      HIPCHK(hipStreamSynchronize(st));          // an earlier launch may still be writing the old records
-      // A HIP graph captured from this batch (pose_off) holds the OLD buffers' addresses in its kernel arguments — a replay after this
-      // point would write freed memory: such buffers are retired (freed with the batch), not freed
-      if (b->pose_off) { if (b->fposeR) b->retired.push_back(b->fposeR); if (b->fposeD) b->retired.push_back(b->fposeD); }
-      else { (void)hipFree(b->fposeR); (void)hipFree(b->fposeD); }
-      b->fposeR = nullptr; b->fposeD = nullptr; b->fpose_frames = 0;
-      if (hipMalloc(&b->fposeR, (size_t)nframes * b->B * b->nspt * TP_R_SIZE * b->esz) != hipSuccess ||
-          hipMalloc((void**)&b->fposeD, (size_t)nframes * b->B * b->nspt * TP_D_SIZE * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFree(b->fposeR); b->fposeR = nullptr; b->fposeD = nullptr; defer = false;
-      } else b->fpose_frames = nframes;
+      // (a graph captured from ANY launch of this batch, pose_off, may name the old records)
+      const size_t nrec = (size_t)nframes * b->B * b->nspt;
+      const int rc = grow_buffers(b, st, b->pose_off != 0, {{b->fposeR, nrec * TP_R_SIZE * b->esz}, {b->fposeD, nrec * TP_D_SIZE * sizeof(double)}});
+      if (rc > 0) return rc;
+      b->fpose_frames = rc ? 0 : nframes;
+      if (rc) defer = false;      // no memory for them: the in-kernel read-out
     }
   }
   if (defer) { a.fposeR = (R*)b->fposeR; a.fposeD = b->fposeD; }
@@ -965,14 +862,19 @@ static PgLayout pg_layout(const tsim_batch* b, int n) {
   const int most = std::max(1, std::min(n, want)), chunk_len = (n + most - 1) / most;
   return {(n + chunk_len - 1) / chunk_len, chunk_len, most};
 }
+// what every pass over (environment, chunk of sub-steps) slots takes from the batch: its view of the model, the window of n sub-steps that ends
+// at the tape's newest record, and the chunk layout
+template <class R> static void pg_common(const tsim_batch* b, PgCommon<R>& p, int n, int nchunk, int chunk_len) {
+  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = n; p.t_end = b->t_cur;
+  p.tape = (const R*)b->tape; p.nchunk = nchunk; p.chunk_len = chunk_len; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
+}
 // A parameter pass of an adjoint launch (tsim_set_param_grad): the pass's kernel (TsLaunch::run picks it by the type of p, whose own fields the
 // caller has set) over the sub-steps the launch just undid, then the fixed-order reduction of its partial sums into the caller's buffer
 template <class R, class Args>
 static int launch_param_pass(tsim_batch* b, TsKernel kernel, const char* name, const char* no_part, Args& p, int n, void* part, const PgSeg (&seg)[3], hipStream_t st) {
   const PgLayout lay = pg_layout(b, n);
-  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = n; p.t_end = b->t_cur;
-  p.tape = (const R*)b->tape; p.z = (const R*)b->zbuf; p.nchunk = lay.nchunk; p.chunk_len = lay.chunk_len;
-  p.P = seg[0].count + seg[1].count + seg[2].count; p.part = (R*)part; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
+  pg_common<R>(b, p, n, lay.nchunk, lay.chunk_len);
+  p.z = (const R*)b->zbuf; p.P = seg[0].count + seg[1].count + seg[2].count; p.part = (R*)part;
   if (!part || p.nchunk > b->pg_chunks) return fail(no_part);
   TsPlan plan = ts_plan(b, kernel, false, 0);
   plan.grid *= p.nchunk;
@@ -1044,12 +946,9 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
 // With a body group on (tsim_set_param_grad_groups) and dtables given, k_tangent_body_src runs first, into the batch's workspace (launch_tangent).
 // the plan of a tangent launch of ndir directions: ts_plan's shape, its LDS grown by the launch's own tangent blocks (ctx_lds: the contexts' part,
 // where the blocks begin).  launch_tangent and tsim_tangent_launch_info both take it from here
-static TsPlan tangent_plan(const tsim_batch* b, int ndir, bool with_dtab, size_t* ctx_lds, int kernel = TS_K_TANGENT) {
-  TsPlan plan = ts_plan(b, kernel, false, 0);
-  *ctx_lds = plan.lds;
+static SlotPlan tangent_plan(const tsim_batch* b, int ndir, bool with_dtab, int kernel = TS_K_TANGENT) {
   const int nhist = b->I[TSIM_IH_INTEGRATOR] == 2 ? 4 : 2, P = with_dtab ? ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr) : 0;
-  plan.lds += (((size_t)(TS_WAVE / plan.lpe) * ts_tan_slot_reals(b->nr, b->nu, P, nhist, ndir) * b->esz + 15) / 16) * 16;
-  return plan;
+  return slot_block_plan(b, ts_plan(b, kernel, false, 0), 0, ts_tan_slot_reals(b->nr, b->nu, P, nhist, ndir));
 }
 // what a tangent launch takes from the batch and the caller (launch_tangent, and the closed-loop launch in tsim_env_push.h)
 template <class R>
@@ -1069,26 +968,22 @@ static int launch_tangent_body_src(tsim_batch* b, TanArgs<R>& a, hipStream_t st,
   if (!a.dtab || !(b->pg_groups & ~TS_PG_CONTACT)) return 0;
   const int ndir = a.ndir;
   const size_t need = (size_t)ndir * a.n * b->B * b->nr;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  const bool cap = capturing(st);
   if (need > b->tan_src_reals) {      // the one allocation of a tangent call: the first that needs the workspace, or needs it larger
-    if (capturing)
+    if (cap)
       return fail(std::string(who) + ": the body columns' workspace must grow, which a stream capture cannot do: call once with these sizes before capturing");
-    HIPCHK(hipStreamSynchronize(st));          // an earlier launch may still be reading the old workspace
-    // A graph captured from a launch below holds the OLD workspace's address in the arguments of k_tangent_body_src and the tangent kernel — a replay
-    // after this point would write freed memory: such a workspace is retired (freed with the batch), not freed
-    if (b->tan_src_captured) { if (b->tan_src) b->retired.push_back(b->tan_src); b->tan_src_captured = 0; }
-    else (void)hipFree(b->tan_src);
-    b->tan_src = nullptr; b->tan_src_reals = 0;
-    if (hipMalloc(&b->tan_src, need * b->esz) != hipSuccess) { (void)hipGetLastError(); b->tan_src = nullptr; return fail(std::string(who) + ": hipMalloc of the body columns' workspace failed"); }
-    b->tan_src_reals = need;
+    // (a graph captured from a launch below names the workspace in the arguments of k_tangent_body_src and the tangent kernel: tan_src_captured)
+    const int rc = grow_buffers(b, st, b->tan_src_captured != 0, {{b->tan_src, need * b->esz}});
+    if (rc > 0) return rc;
+    b->tan_src_captured = 0;
+    b->tan_src_reals = rc ? 0 : need;
+    if (rc) return fail(std::string(who) + ": hipMalloc of the body columns' workspace failed");
   }
   const PgLayout lay = pg_layout(b, a.n);
   TanBodyArgs<R> p{};
-  p.I = b->dI; p.F = (const R*)b->dF; p.Fenv = (const R*)b->dFenv; p.fstride = b->nfrec; p.B = b->B; p.n = a.n; p.t_end = b->t_cur;
-  p.tape = (const R*)b->tape; p.nchunk = lay.nchunk; p.chunk_len = lay.chunk_len; p.stage_cpt = b->stage_cpt; p.tk = b->tape_k;
+  pg_common<R>(b, p, a.n, lay.nchunk, lay.chunk_len);
   p.groups = b->pg_groups; p.ndir = ndir; p.dtab = a.dtab; p.src = (R*)b->tan_src;
-  if (capturing) b->tan_src_captured = 1;      // a graph now names this workspace
+  if (cap) b->tan_src_captured = 1;      // a graph now names this workspace
   TsPlan bp = ts_plan(b, TS_K_TANGENT_BODY, false, 0);
   bp.grid *= p.nchunk;
   if (!TsLaunch<void, false, R>::run(bp, st, p)) return fail("no k_tangent_body_src instantiation for the launch plan");
@@ -1101,8 +996,7 @@ static int launch_tangent(tsim_batch* b, int T, int S, int ndir, const int32_t* 
                           void* dq_out, void* dqd_out, void* dvar_out, void* dtac_out, hipStream_t st) {
   TanArgs<R> a{};
   tangent_args<R>(b, a, T, S, ndir, tac_slot, du, dq0, dqd0, dtab, dq_out, dqd_out, dvar_out, dtac_out);
-  size_t ctx_lds;
-  const TsPlan plan = tangent_plan(b, ndir, dtab != nullptr, &ctx_lds);
+  const auto [plan, ctx_lds] = tangent_plan(b, ndir, dtab != nullptr);
   a.xoff = (int)(ctx_lds / b->esz);
   if (plan.lds > TS_TAN_LDS_CAP) return fail("tangent_episode: the tangent state of " + std::to_string(ndir) + " directions does not fit the block's LDS for this model");
   if (int rc = launch_tangent_body_src<R>(b, a, st, "tangent_episode")) return rc;
@@ -1114,27 +1008,36 @@ static int launch_tangent(tsim_batch* b, int T, int S, int ndir, const int32_t* 
 // The per-frame transition Jacobians over the newest T x S taped sub-steps (tsim_frame_jacobians): one launch of the generic k_frame_jacobian,
 // T x ceil(B / NS) blocks, whatever the batch's view, on the batch's per-environment rows.  Reads the tape, writes the caller's buffers.
 // the plan: ts_plan's shape for ONE frame, its LDS grown by the slots' blocks (ctx_lds: the contexts' part, where the blocks begin)
-static TsPlan frame_jacobian_plan(const tsim_batch* b, size_t* ctx_lds) {
-  TsPlan plan = ts_plan(b, TS_K_FRAME_JACOBIAN, false, 0);
-  *ctx_lds = plan.lds;
-  plan.lds += (((size_t)(TS_WAVE / plan.lpe) * ts_fj_slot_reals(b->nr, b->nu) * b->esz + 15) / 16) * 16;
-  return plan;
-}
+static SlotPlan frame_jacobian_plan(const tsim_batch* b) { return slot_block_plan(b, ts_plan(b, TS_K_FRAME_JACOBIAN, false, 0), 0, ts_fj_slot_reals(b->nr, b->nu)); }
 template <class R>
 static int launch_frame_jacobians(tsim_batch* b, int T, int S, void* A_out, void* B_out, void* Jvar_out, hipStream_t st) {
-  size_t ctx_lds;
-  TsPlan plan = frame_jacobian_plan(b, &ctx_lds);
+  auto [plan, ctx_lds] = frame_jacobian_plan(b);
   if (plan.lds > TS_TAN_LDS_CAP) return fail("frame_jacobians: the " + std::to_string(ts_fj_ncol(b->nr, b->nu)) + " columns of an environment do not fit the block's LDS for this model");
   if ((unsigned long long)plan.grid * (unsigned)T > 0x7fffffffull) return fail("frame_jacobians: too many blocks");
   FjArgs<R> a{};
-  a.I = b->dI; a.F = (const R*)b->dF; a.Fenv = (const R*)b->dFenv; a.fstride = b->nfrec; a.B = b->B; a.n = T * S; a.t_end = b->t_cur;
-  a.tape = (const R*)b->tape; a.nchunk = T; a.chunk_len = S; a.stage_cpt = b->stage_cpt; a.tk = b->tape_k; a.cull = b->pair_cull;
-  a.xoff = (int)(ctx_lds / b->esz);
+  pg_common<R>(b, a, T * S, T, S);      // a chunk is a frame
+  a.cull = b->pair_cull; a.xoff = (int)(ctx_lds / b->esz);
   a.A_out = (R*)A_out; a.B_out = (R*)B_out; a.Jvar_out = (R*)Jvar_out;
   plan.grid *= (unsigned)T;
   if (!TsLaunch<void, false, R>::run(plan, st, a)) return fail("no k_frame_jacobian instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// The checks the episode entry points share; who: the entry point, in front of the message.
+static int frames_positive(const std::string& who, int num_frames, int num_steps) {
+  return num_frames <= 0 || num_steps <= 0 ? fail(who + ": num_frames and num_steps must be positive") : 0;
+}
+// the window of num_frames x num_steps sub-steps (*n) is on the tape: the newest ones
+static int taped_window(const tsim_batch* b, const std::string& who, int num_frames, int num_steps, long long* n) {
+  if (int rc = frames_positive(who, num_frames, num_steps)) return rc;
+  *n = (long long)num_frames * num_steps;
+  return *n > b->t_cur ? fail(who + ": only " + std::to_string(b->t_cur) + " sub-steps on the tape") : 0;
+}
+// the tangent passes carry nothing across calls: a BDF2 model's window is the whole tape
+static int bdf2_window_is_the_tape(const tsim_batch* b, const std::string& who, long long n) {
+  if (b->I[TSIM_IH_INTEGRATOR] != 2 || n == b->t_cur) return 0;
+  return fail(who + ": a BDF2 model's window must start at tape record 0 (no tangent is carried across calls); the tape holds " + std::to_string(b->t_cur) + " sub-steps");
 }
 
 extern "C" {
@@ -1166,7 +1069,7 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   b->nl = nl; b->nr = nr; b->nu = nu; b->nvar = I[TSIM_IH_NVAR]; b->ntax = I[TSIM_IH_NTAXEL];
   b->esz = dtype == TSIM_F32 ? 4 : 8;
   b->t_cur = 0; b->record = 0; b->has_exp = n_exp > 0;
-  b->dFenv = nullptr; b->nfrec = I[TSIM_IH_FOFF_CPT];
+  b->nfrec = I[TSIM_IH_FOFF_CPT];
   b->lpe_forced = 0;
   { const std::vector<int32_t> S_ = build_sched(b->I, b->F); b->nsched = (int)S_.size(); b->tt_off = b->I[TSIM_IH_NI] + S_[TS_SCHED_TAXTAB]; }
   b->pair_cull = getenv("TSIM_NO_PAIR_CULL") ? 0 : 1;
@@ -1193,7 +1096,7 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   b->rec = ts_rec(nr, nu, (int)b->esz, b->tape_k);
   if (lds_bytes_for(b, 1) > 64 * 1024) { delete b; return fail("model needs more than 64 KiB of LDS per environment"); }
   decide_stage_cpt(b);
-  b->dI = nullptr; b->dF = nullptr; b->tape = nullptr; b->lamq = nullptr; b->lamv = nullptr; b->evals = nullptr; b->order = nullptr; b->order_valid = 0; b->prev = nullptr; b->has_prev = 0; b->poseR = nullptr; b->poseD = nullptr; b->nspt = b->I[TSIM_IH_NSPRIM];
+  b->nspt = b->I[TSIM_IH_NSPRIM];
   size_t tape_bytes = (size_t)(tape_capacity + 1) * B * b->rec * b->esz;
   if (hipMalloc(&b->dI, (b->I.size() + b->nsched) * sizeof(int32_t)) != hipSuccess || hipMalloc(&b->dF, b->F.size() * b->esz) != hipSuccess ||
       hipMalloc(&b->tape, tape_bytes) != hipSuccess || hipMalloc(&b->lamq, (size_t)2 * B * nr * b->esz) != hipSuccess ||
@@ -1217,9 +1120,8 @@ void tsim_batch_destroy(tsim_batch* b) {
   for (void* p : b->retired) (void)hipFree(p);
   for (auto& k : b->kt) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
   for (hipEvent_t e : b->kt_free) (void)hipEventDestroy(e);
-  (void)hipFree(b->dFenv); (void)hipFree(b->dI); (void)hipFree(b->dF); (void)hipFree(b->tape); (void)hipFree(b->lamq); (void)hipFree(b->lamv); (void)hipFree(b->evals); (void)hipFree(b->helped); (void)hipFree(b->gnorm); (void)hipFree(b->order); (void)hipFree(b->order_ep); (void)hipFree(b->prev); (void)hipFree(b->poseR); (void)hipFree(b->poseD); (void)hipFree(b->fposeR); (void)hipFree(b->fposeD); (void)hipFree(b->dKmask); (void)hipFree(b->dFlag);
-  (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); (void)hipFree(b->pgbpart); (void)hipFree(b->pg_slots); (void)hipFree(b->tan_src);
-  delete b;
+  (void)hipFree(b->tape);
+  delete b;      // the buffers the batch owns (DevBuf) go with it, on the batch's device: guard_ is still in scope
 }
 
 int tsim_ndof_r(const tsim_batch* b) { return b->nr; }
@@ -1230,25 +1132,15 @@ int tsim_batch_size(const tsim_batch* b) { return b->B; }
 int tsim_dtype(const tsim_batch* b) { return b->dtype; }
 double tsim_timestep(const tsim_batch* b) { return b->F[TSIM_FH_H]; }
 int tsim_tape_len(const tsim_batch* b) { return b->record ? b->t_cur : 0; }
-int tsim_launch_info(const tsim_batch* b, int32_t* out) {
-  const LaunchShape L = launch_shape(b, b->lpe_forced);
-  out[0] = (int32_t)L.lds; out[1] = TS_WAVE; out[2] = (int32_t)L.grid; out[3] = L.lpe;
-  return 0;
-}
+int tsim_launch_info(const tsim_batch* b, int32_t* out) { return plan_info(ts_plan(b, TS_K_FORWARD, false, 0), out); }      // (launch_shape at the batch's lanes)
 int tsim_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, int32_t* out) {
   if (!b || !out) return fail("tangent_launch_info: null argument");
   if (ndir < 1 || ndir > TSIM_TANGENT_MAX_DIR) return fail("tangent_launch_info: ndir must be 1 .. " + std::to_string((int)TSIM_TANGENT_MAX_DIR));
-  size_t ctx_lds;
-  const TsPlan p = tangent_plan(b, ndir, with_dtables != 0, &ctx_lds);
-  out[0] = (int32_t)p.lds; out[1] = TS_WAVE; out[2] = (int32_t)p.grid; out[3] = p.lpe;
-  return 0;
+  return plan_info(tangent_plan(b, ndir, with_dtables != 0).plan, out);
 }
 int tsim_frame_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
   if (!b || !out) return fail("frame_jacobians_launch_info: null argument");
-  size_t ctx_lds;
-  const TsPlan p = frame_jacobian_plan(b, &ctx_lds);
-  out[0] = (int32_t)p.lds; out[1] = TS_WAVE; out[2] = (int32_t)p.grid; out[3] = p.lpe;
-  return 0;
+  return plan_info(frame_jacobian_plan(b).plan, out);
 }
 int tsim_kernel_timing(tsim_batch* b, int enable) { b->kt_on = enable ? 1 : 0; return 0; }
 int tsim_kernel_times(tsim_batch* b, double* ms_sum, int32_t* launches) {
@@ -1268,8 +1160,7 @@ int tsim_kernel_times(tsim_batch* b, double* ms_sum, int32_t* launches) {
 int tsim_set_lanes_per_env(tsim_batch* b, int lanes) {
   if (lanes != 0 && lanes != 16 && lanes != 32 && lanes != 64) return fail("set_lanes_per_env: 0 (automatic), 16, 32 or 64");
   b->lpe_forced = lanes;
-  b->order_valid = 0; b->order_ep_n = 0;
-  decide_stage_cpt(b);      // depends on the shape; the flag travels with every launch as a kernel argument: nothing on the device to update
+  shape_changed(b);
   return 0;
 }
 int tsim_static_model(const tsim_batch* b) { return kernel_mode(b, b->lpe_forced) != TS_KM_GENERIC ? b->static_id : 0; }
@@ -1281,8 +1172,7 @@ const char* tsim_kernel_variant(const tsim_batch* b) {
 }
 int tsim_set_static(tsim_batch* b, int allow) {
   b->no_static = allow ? 0 : 1;
-  b->order_valid = 0; b->order_ep_n = 0;
-  decide_stage_cpt(b);      // the launch shape depends on which kernels run
+  shape_changed(b);      // the launch shape depends on which kernels run
   return 0;
 }
 int tsim_set_option(tsim_batch* b, int option, int value) {
@@ -1331,17 +1221,16 @@ int tsim_update_model(tsim_batch* b, const int32_t* I, const double* F, void* st
   TS_DEVICE(b);
   pose_invalidate(b, (hipStream_t)stream);
   b->I.assign(I, I + I[TSIM_IH_NI]); b->F.assign(F, F + I[TSIM_IH_NF]);
-  if (b->dFenv) { HIPCHK(hipFree(b->dFenv)); b->dFenv = nullptr; b->env_struct_ok = 0; }     // per-environment tables refer to the old model
+  if (b->dFenv) { HIPCHK(hipFree(b->dFenv)); (void)b->dFenv.take(); b->env_struct_ok = 0; }     // per-environment tables refer to the old model
   if (int rc = upload_model(b, (hipStream_t)stream)) return rc;
-  b->order_valid = 0; b->order_ep_n = 0;
-  decide_stage_cpt(b);      // the edit may have moved the batch between the compiled-in and the generic kernels: another launch shape
+  shape_changed(b);      // the edit may have moved the batch between the compiled-in and the generic kernels: another launch shape
   return 0;
 }
 
 int tsim_set_env_tables(tsim_batch* b, const void* tables, void* stream) {
   TS_DEVICE(b);
   pose_invalidate(b, (hipStream_t)stream);
-  if (!tables) { if (b->dFenv) { HIPCHK(hipFree(b->dFenv)); b->dFenv = nullptr; b->env_struct_ok = 0; decide_stage_cpt(b); } return 0; }
+  if (!tables) { if (b->dFenv) { HIPCHK(hipFree(b->dFenv)); (void)b->dFenv.take(); b->env_struct_ok = 0; decide_stage_cpt(b); } return 0; }      // (the block orders stay: see profiles/r24_host_launch_layer.md)
   size_t bytes = (size_t)b->B * b->nfrec * b->esz;
   const bool fresh = !b->dFenv;
   if (fresh) HIPCHK(hipMalloc(&b->dFenv, bytes));
@@ -1351,8 +1240,7 @@ int tsim_set_env_tables(tsim_batch* b, const void* tables, void* stream) {
   // is overwritten with the shared model's.
   {
     const unsigned nh = (unsigned)((b->B * TSIM_FH_SIZE + 255) / 256);
-    if (b->dtype == TSIM_F32) hipLaunchKernelGGL(k_env_header<float>, dim3(nh), dim3(256), 0, (hipStream_t)stream, (float*)b->dFenv, (const float*)b->dF, b->nfrec, b->B);
-    else hipLaunchKernelGGL(k_env_header<double>, dim3(nh), dim3(256), 0, (hipStream_t)stream, (double*)b->dFenv, (const double*)b->dF, b->nfrec, b->B);
+    by_real(b, [&](auto r) { using R = decltype(r); hipLaunchKernelGGL(k_env_header<R>, dim3(nh), dim3(256), 0, (hipStream_t)stream, (R*)b->dFenv, (const R*)b->dF, b->nfrec, b->B); });
     HIPCHK(hipGetLastError());
   }
   // A batch whose model has a compiled-in structure stays on that instantiation if every environment's table keeps the structural floats
@@ -1360,26 +1248,23 @@ int tsim_set_env_tables(tsim_batch* b, const void* tables, void* stream) {
   // 4-byte read-back (this call synchronises then; inside a stream capture the check is skipped and the batch takes the generic kernels).
   const int ok_before = b->env_struct_ok;
   b->env_struct_ok = 0;
-  if (b->static_id != 0 && b->dtype == TSIM_F32) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
-      if (!b->dKmask) {
-        std::vector<unsigned char> km(b->nfrec);
-        for (int i = 0; i < b->nfrec; ++i) km[i] = TsParam<TsStaticPusher>::Fk(i) ? 1 : 0;
-        HIPCHK(hipMalloc((void**)&b->dKmask, km.size())); HIPCHK(hipMalloc((void**)&b->dFlag, sizeof(int)));
-        HIPCHK(hipMemcpy(b->dKmask, km.data(), km.size(), hipMemcpyHostToDevice));
-      }
-      int flag = 0;
-      HIPCHK(hipMemsetAsync(b->dFlag, 0, sizeof(int), (hipStream_t)stream));
-      const size_t n = (size_t)b->B * b->nfrec;
-      hipLaunchKernelGGL(k_check_structure, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)b->dFenv, (const float*)b->dF, b->dKmask, b->nfrec, n, b->dFlag);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(&flag, b->dFlag, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-      HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-      b->env_struct_ok = flag == 0;
+  if (b->static_id != 0 && b->dtype == TSIM_F32 && !capturing((hipStream_t)stream)) {
+    if (!b->dKmask) {
+      std::vector<unsigned char> km(b->nfrec);
+      for (int i = 0; i < b->nfrec; ++i) km[i] = TsParam<TsStaticPusher>::Fk(i) ? 1 : 0;
+      HIPCHK(hipMalloc((void**)&b->dKmask, km.size())); HIPCHK(hipMalloc((void**)&b->dFlag, sizeof(int)));
+      HIPCHK(hipMemcpy(b->dKmask, km.data(), km.size(), hipMemcpyHostToDevice));
     }
+    int flag = 0;
+    HIPCHK(hipMemsetAsync(b->dFlag, 0, sizeof(int), (hipStream_t)stream));
+    const size_t n = (size_t)b->B * b->nfrec;
+    hipLaunchKernelGGL(k_check_structure, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)b->dFenv, (const float*)b->dF, b->dKmask, b->nfrec, n, b->dFlag);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&flag, b->dFlag, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    b->env_struct_ok = flag == 0;
   }
-  if (fresh || ok_before != b->env_struct_ok) { b->order_valid = 0; b->order_ep_n = 0; decide_stage_cpt(b); }      // the block's LDS layout / the kernels change
+  if (fresh || ok_before != b->env_struct_ok) shape_changed(b);      // the block's LDS layout / the kernels change
   return 0;
 }
 int tsim_table_size(const tsim_batch* b) { return b->nfrec; }
@@ -1398,13 +1283,13 @@ static int pg_alloc(tsim_batch* b) {
   };
   if (body && !get(&b->pgbpart, (size_t)chunks * ts_pgb_count(b->I[TSIM_IH_NL], b->nu, b->nr))) return fail("set_param_grad_groups: hipMalloc failed");
   if (!get(&b->zbuf, (size_t)b->cap * b->nr) || !get(&b->pgpart, (size_t)chunks * ts_pg_count(b->I[TSIM_IH_NPAIR], b->I[TSIM_IH_NSENSOR], b->nr))) {
-    (void)hipFree(b->zbuf); (void)hipFree(b->pgpart); b->zbuf = nullptr; b->pgpart = nullptr;
+    b->zbuf.release(); b->pgpart.release();
     return fail("set_param_grad: hipMalloc failed");
   }
   b->pg_chunks = chunks;
   // ... and the closed-loop adjoint's frame -> seed row table: at most one frame per taped sub-step
   if (!b->pg_slots && hipMalloc((void**)&b->pg_slots, std::max<size_t>((size_t)b->cap * sizeof(int32_t), 8)) != hipSuccess) {
-    (void)hipGetLastError(); b->pg_slots = nullptr;
+    (void)hipGetLastError(); (void)b->pg_slots.take();
     return fail("set_param_grad: hipMalloc failed");
   }
   return 0;
@@ -1436,8 +1321,7 @@ int tsim_reset(tsim_batch* b, const void* q0, const void* qd0, int backward_flag
   TS_DEVICE(b);
   hipStream_t st = (hipStream_t)stream;
   int n = b->B * b->nr, blk = 256, grd = (n + blk - 1) / blk;
-  if (b->dtype == TSIM_F32) hipLaunchKernelGGL(k_set_state<float>, dim3(grd), dim3(blk), 0, st, (float*)b->tape, (const float*)q0, (const float*)qd0, b->B, b->nr, b->rec);
-  else hipLaunchKernelGGL(k_set_state<double>, dim3(grd), dim3(blk), 0, st, (double*)b->tape, (const double*)q0, (const double*)qd0, b->B, b->nr, b->rec);
+  by_real(b, [&](auto r) { using R = decltype(r); hipLaunchKernelGGL(k_set_state<R>, dim3(grd), dim3(blk), 0, st, (R*)b->tape, (const R*)q0, (const R*)qd0, b->B, b->nr, b->rec); });
   HIPCHK(hipGetLastError());
   if (zero_async(b->lamq, (size_t)2 * b->B * b->nr * b->esz, st) || zero_async(b->lamv, (size_t)2 * b->B * b->nr * b->esz, st)) return 1;
   b->t_cur = 0; b->record = backward_flag ? 1 : 0; b->order_valid = 0; b->has_prev = 0; b->tape_k_ok = b->tape_k;
@@ -1454,9 +1338,11 @@ int tsim_reset_masked(tsim_batch* b, const void* q0, const void* qd0, const int3
   int n = b->B * b->nr, blk = 256, grd = (n + blk - 1) / blk;
   size_t off = (size_t)b->t_cur * b->B * b->rec;
   // BDF2 models: the environment restarts with a constant-velocity history (q_-1 = q0 - h qd0, qd_-1 = qd0) [CHOICE]
-  void* prev = (b->I[TSIM_IH_INTEGRATOR] == 2 && b->has_prev) ? b->prev : nullptr;
-  if (b->dtype == TSIM_F32) hipLaunchKernelGGL(k_set_state_masked<float>, dim3(grd), dim3(blk), 0, st, (float*)b->tape + off, (const float*)q0, (const float*)qd0, mask, (double*)prev, (float)b->F[TSIM_FH_H], b->B, b->nr, b->rec);
-  else hipLaunchKernelGGL(k_set_state_masked<double>, dim3(grd), dim3(blk), 0, st, (double*)b->tape + off, (const double*)q0, (const double*)qd0, mask, (double*)prev, b->F[TSIM_FH_H], b->B, b->nr, b->rec);
+  double* prev = (b->I[TSIM_IH_INTEGRATOR] == 2 && b->has_prev) ? (double*)b->prev : nullptr;
+  by_real(b, [&](auto r) {
+    using R = decltype(r);
+    hipLaunchKernelGGL(k_set_state_masked<R>, dim3(grd), dim3(blk), 0, st, (R*)b->tape + off, (const R*)q0, (const R*)qd0, mask, prev, (R)b->F[TSIM_FH_H], b->B, b->nr, b->rec);
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1466,9 +1352,7 @@ int tsim_step(tsim_batch* b, const void* u, int num_steps, void* q_out, void* qd
   if (!u && b->nu > 0) return fail("step: u is null");
   if (b->record && b->t_cur + num_steps > b->cap) return fail("step: tape capacity exceeded (" + std::to_string(b->cap) + " sub-steps)");
   TS_DEVICE(b);
-  int rc = b->dtype == TSIM_F32 ? launch_forward<float>(b, u, 1, nullptr, num_steps, q_out, qd_out, var_out, tac_out, status, (hipStream_t)stream)
-                                : launch_forward<double>(b, u, 1, nullptr, num_steps, q_out, qd_out, var_out, tac_out, status, (hipStream_t)stream);
-  if (rc) return rc;
+  if (int rc = by_real(b, [&](auto r) { return launch_forward<decltype(r)>(b, u, 1, nullptr, num_steps, q_out, qd_out, var_out, tac_out, status, (hipStream_t)stream); })) return rc;
   if (b->record) b->t_cur += num_steps;
   b->has_prev = 1;
   return 0;
@@ -1478,8 +1362,7 @@ int tsim_get_state(tsim_batch* b, void* q_out, void* qd_out, void* stream) {
   TS_DEVICE(b);
   int n = b->B * b->nr, blk = 256, grd = (n + blk - 1) / blk;
   size_t off = (size_t)b->t_cur * b->B * b->rec;
-  if (b->dtype == TSIM_F32) hipLaunchKernelGGL(k_get_state<float>, dim3(grd), dim3(blk), 0, (hipStream_t)stream, (const float*)b->tape + off, (float*)q_out, (float*)qd_out, b->B, b->nr, b->rec);
-  else hipLaunchKernelGGL(k_get_state<double>, dim3(grd), dim3(blk), 0, (hipStream_t)stream, (const double*)b->tape + off, (double*)q_out, (double*)qd_out, b->B, b->nr, b->rec);
+  by_real(b, [&](auto r) { using R = decltype(r); hipLaunchKernelGGL(k_get_state<R>, dim3(grd), dim3(blk), 0, (hipStream_t)stream, (const R*)b->tape + off, (R*)q_out, (R*)qd_out, b->B, b->nr, b->rec); });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1491,20 +1374,17 @@ int tsim_readout(tsim_batch* b, void* var_out, void* tac_out, void* stream) {
   // taxels that are paired with no primitive (a sensor body without a general_primitive_contact) read zero, as in k_forward's read-out
   if (tac_out && b->ntax > 0 && b->nspt == 0 && zero_async(tac_out, (size_t)b->B * 3 * b->ntax * b->esz, st)) return 1;
   if (tac && (b->nspt > TX_MAXK || b->I[TSIM_IH_NSENSOR] > TX_MAXS)) return fail("readout: more than " + std::to_string((int)TX_MAXK) + " (sensor, primitive) combinations or " + std::to_string((int)TX_MAXS) + " sensors (k_taxels staging)");
-  {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { b->pose_off = 1; b->pose_valid = 0; }
-  }
+  if (capturing(st)) { b->pose_off = 1; b->pose_valid = 0; }
   const bool fk = var_out || !tac || !b->pose_valid;      // the forward launch left the pose records of this state: k_taxels alone
-  if (b->dtype == TSIM_F32) {
-    ReadArgs<float> a{b->dI, (const float*)b->dF, (const float*)b->dFenv, b->nfrec, b->B, b->t_cur, (const float*)b->tape, (float*)var_out, tac ? (float*)b->poseR : nullptr, b->poseD, b->nspt, b->stage_cpt, b->tape_k};
-    if (fk) hipLaunchKernelGGL(k_readout<float>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), st, a);
-    if (tac) { KtScope kt_(b, TSIM_KT_TAXELS, st); if (launch_taxels<float>(b, b->poseR, b->poseD, 1, nullptr, tac_out, st)) return 1; }
-  } else {
-    ReadArgs<double> a{b->dI, (const double*)b->dF, (const double*)b->dFenv, b->nfrec, b->B, b->t_cur, (const double*)b->tape, (double*)var_out, tac ? (double*)b->poseR : nullptr, b->poseD, b->nspt, b->stage_cpt, b->tape_k};
-    if (fk) hipLaunchKernelGGL(k_readout<double>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), st, a);
-    if (tac) { KtScope kt_(b, TSIM_KT_TAXELS, st); if (launch_taxels<double>(b, b->poseR, b->poseD, 1, nullptr, tac_out, st)) return 1; }
-  }
+  const int rc = by_real(b, [&](auto r) {
+    using R = decltype(r);
+    ReadArgs<R> a{b->dI, (const R*)b->dF, (const R*)b->dFenv, b->nfrec, b->B, b->t_cur, (const R*)b->tape, (R*)var_out, tac ? (R*)b->poseR : nullptr, b->poseD, b->nspt, b->stage_cpt, b->tape_k};
+    if (fk) hipLaunchKernelGGL(k_readout<R>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), st, a);
+    if (!tac) return 0;
+    KtScope kt_(b, TSIM_KT_TAXELS, st);
+    return launch_taxels<R>(b, b->poseR, b->poseD, 1, nullptr, tac_out, st);
+  });
+  if (rc) return rc;
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1516,22 +1396,18 @@ int tsim_backward_steps(tsim_batch* b, int n, int seed_mode, const void* df_dq, 
   if (seed_mode != 0 && seed_mode != 1) return fail("backward_steps: bad seed_mode");
   TS_DEVICE(b);
   const int stride = seed_mode == 1 ? 1 : n;
-  int rc = b->dtype == TSIM_F32 ? launch_backward<float>(b, n, stride, 0, nullptr, df_dq, df_dvar, df_dtac, df_du, (hipStream_t)stream)
-                                : launch_backward<double>(b, n, stride, 0, nullptr, df_dq, df_dvar, df_dtac, df_du, (hipStream_t)stream);
-  if (rc) return rc;
+  if (int rc = by_real(b, [&](auto r) { return launch_backward<decltype(r)>(b, n, stride, 0, nullptr, df_dq, df_dvar, df_dtac, df_du, (hipStream_t)stream); })) return rc;
   b->t_cur -= n;
   pose_invalidate(b, (hipStream_t)stream);      // the pose records a forward launch left are those of the state before the roll-back
   return 0;
 }
 
 int tsim_rollout(tsim_batch* b, const void* u, int num_frames, int num_steps, const int32_t* tactile_slot, void* q_out, void* qd_out, void* var_out, void* tac_out, int32_t* status, void* stream) {
-  if (num_frames <= 0 || num_steps <= 0) return fail("rollout: num_frames and num_steps must be positive");
+  if (int rc = frames_positive("rollout", num_frames, num_steps)) return rc;
   if (!u && b->nu > 0) return fail("rollout: u is null");
   if (b->record && b->t_cur + (long long)num_frames * num_steps > b->cap) return fail("rollout: tape capacity exceeded (" + std::to_string(b->cap) + " sub-steps)");
   TS_DEVICE(b);
-  int rc = b->dtype == TSIM_F32 ? launch_forward<float>(b, u, num_frames, tactile_slot, num_steps, q_out, qd_out, var_out, tac_out, status, (hipStream_t)stream)
-                                : launch_forward<double>(b, u, num_frames, tactile_slot, num_steps, q_out, qd_out, var_out, tac_out, status, (hipStream_t)stream);
-  if (rc) return rc;
+  if (int rc = by_real(b, [&](auto r) { return launch_forward<decltype(r)>(b, u, num_frames, tactile_slot, num_steps, q_out, qd_out, var_out, tac_out, status, (hipStream_t)stream); })) return rc;
   if (b->record) b->t_cur += num_frames * num_steps;
   b->has_prev = 1;
   return 0;
@@ -1539,14 +1415,11 @@ int tsim_rollout(tsim_batch* b, const void* u, int num_frames, int num_steps, co
 
 int tsim_backward_episode(tsim_batch* b, int num_frames, int num_steps, const int32_t* tactile_slot, const void* df_dq, const void* df_dvar, const void* df_dtac, void* df_du, void* stream) {
   if (!b->record) return fail("backward_episode: reset(backward_flag=True) was not called");
-  if (num_frames <= 0 || num_steps <= 0) return fail("backward_episode: num_frames and num_steps must be positive");
-  const long long n = (long long)num_frames * num_steps;
-  if (n > b->t_cur) return fail("backward_episode: only " + std::to_string(b->t_cur) + " sub-steps on the tape");
+  long long n;
+  if (int rc = taped_window(b, "backward_episode", num_frames, num_steps, &n)) return rc;
   if (!df_du && b->nu > 0) return fail("backward_episode: df_du is null");
   TS_DEVICE(b);
-  int rc = b->dtype == TSIM_F32 ? launch_backward<float>(b, (int)n, num_steps, 1, tactile_slot, df_dq, df_dvar, df_dtac, df_du, (hipStream_t)stream)
-                                : launch_backward<double>(b, (int)n, num_steps, 1, tactile_slot, df_dq, df_dvar, df_dtac, df_du, (hipStream_t)stream);
-  if (rc) return rc;
+  if (int rc = by_real(b, [&](auto r) { return launch_backward<decltype(r)>(b, (int)n, num_steps, 1, tactile_slot, df_dq, df_dvar, df_dtac, df_du, (hipStream_t)stream); })) return rc;
   b->t_cur -= (int)n;
   pose_invalidate(b, (hipStream_t)stream);
   return 0;
@@ -1557,27 +1430,22 @@ int tsim_tangent_episode(tsim_batch* b, int num_frames, int num_steps, int ndir,
   if (!b) return fail("tangent_episode: null batch");
   if (ndir < 1 || ndir > TSIM_TANGENT_MAX_DIR) return fail("tangent_episode: ndir must be 1 .. " + std::to_string((int)TSIM_TANGENT_MAX_DIR) + ", got " + std::to_string(ndir));
   if (!b->record || b->t_cur <= 0) return fail("tangent_episode: no tape recorded (reset(backward_flag=True), then a roll-out)");
-  if (num_frames <= 0 || num_steps <= 0) return fail("tangent_episode: num_frames and num_steps must be positive");
-  const long long n = (long long)num_frames * num_steps;
-  if (n > b->t_cur) return fail("tangent_episode: only " + std::to_string(b->t_cur) + " sub-steps on the tape");
-  if (b->I[TSIM_IH_INTEGRATOR] == 2 && n != b->t_cur)
-    return fail("tangent_episode: a BDF2 model's window must start at tape record 0 (no tangent is carried across calls); the tape holds " + std::to_string(b->t_cur) + " sub-steps");
+  long long n;
+  if (int rc = taped_window(b, "tangent_episode", num_frames, num_steps, &n)) return rc;
+  if (int rc = bdf2_window_is_the_tape(b, "tangent_episode", n)) return rc;
   TS_DEVICE(b);
-  return b->dtype == TSIM_F32 ? launch_tangent<float>(b, num_frames, num_steps, ndir, tactile_slot, du, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, (hipStream_t)stream)
-                              : launch_tangent<double>(b, num_frames, num_steps, ndir, tactile_slot, du, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, (hipStream_t)stream);
+  return by_real(b, [&](auto r) { return launch_tangent<decltype(r)>(b, num_frames, num_steps, ndir, tactile_slot, du, dq0, dqd0, dtables, dq_out, dqd_out, dvar_out, dtac_out, (hipStream_t)stream); });
 }
 
 int tsim_frame_jacobians(tsim_batch* b, int num_frames, int num_steps, void* A_out, void* B_out, void* Jvar_out, void* stream) {
   if (!b) return fail("frame_jacobians: null batch");
   if (!b->record || b->t_cur <= 0) return fail("frame_jacobians: no tape recorded (reset(backward_flag=True), then a roll-out)");
-  if (num_frames <= 0 || num_steps <= 0) return fail("frame_jacobians: num_frames and num_steps must be positive");
-  const long long n = (long long)num_frames * num_steps;
-  if (n > b->t_cur) return fail("frame_jacobians: only " + std::to_string(b->t_cur) + " sub-steps on the tape");
+  long long n;
+  if (int rc = taped_window(b, "frame_jacobians", num_frames, num_steps, &n)) return rc;
   if (b->I[TSIM_IH_INTEGRATOR] == 2) return fail("frame_jacobians: a BDF2 model's transition acts on two states of history, which is out of scope");
   if (!A_out && !B_out && !Jvar_out) return 0;
   TS_DEVICE(b);
-  return b->dtype == TSIM_F32 ? launch_frame_jacobians<float>(b, num_frames, num_steps, A_out, B_out, Jvar_out, (hipStream_t)stream)
-                              : launch_frame_jacobians<double>(b, num_frames, num_steps, A_out, B_out, Jvar_out, (hipStream_t)stream);
+  return by_real(b, [&](auto r) { return launch_frame_jacobians<decltype(r)>(b, num_frames, num_steps, A_out, B_out, Jvar_out, (hipStream_t)stream); });
 }
 
 int tsim_get_adjoint(tsim_batch* b, void* df_dq0, void* df_dqd0, void* stream) {
@@ -1642,13 +1510,11 @@ int tsim_debug_signature(tsim_batch* b, int t_first, int n, uint32_t* out, void*
   if (t_first < 0 || n <= 0 || t_first + n > b->t_cur) return fail("debug_signature: sub-steps " + std::to_string(t_first) + "+" + std::to_string(n) + " are not on the tape (" + std::to_string(b->t_cur) + ")");
   if (!out) return fail("debug_signature: out is null");
   TS_DEVICE(b);
-  if (b->dtype == TSIM_F32) {
-    SigArgs<float> a{b->dI, (const float*)b->dF, (const float*)b->dFenv, b->nfrec, b->B, t_first, n, (const float*)b->tape, out, b->stage_cpt, b->tape_k};
-    hipLaunchKernelGGL(k_signature<float>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), (hipStream_t)stream, a);
-  } else {
-    SigArgs<double> a{b->dI, (const double*)b->dF, (const double*)b->dFenv, b->nfrec, b->B, t_first, n, (const double*)b->tape, out, b->stage_cpt, b->tape_k};
-    hipLaunchKernelGGL(k_signature<double>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), (hipStream_t)stream, a);
-  }
+  by_real(b, [&](auto r) {
+    using R = decltype(r);
+    SigArgs<R> a{b->dI, (const R*)b->dF, (const R*)b->dFenv, b->nfrec, b->B, t_first, n, (const R*)b->tape, out, b->stage_cpt, b->tape_k};
+    hipLaunchKernelGGL(k_signature<R>, dim3(b->B), dim3(TS_WAVE), lds_bytes_for(b, 1), (hipStream_t)stream, a);
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1659,14 +1525,11 @@ int tsim_debug_eval(tsim_batch* b, const void* q1, const void* q0, const void* q
   TS_DEVICE(b);
   // the stamped variant of an nr > 8 model: one environment per wavefront whatever the batch's shape (ts_plan: the debug kernel's shape)
   const TsPlan plan = ts_plan(b, TS_K_DEBUG_EVAL, false, cycles && b->nr > 8 ? TS_WAVE : 0);
-  bool ok;
-  if (b->dtype == TSIM_F32) {
-    DbgArgs<float> a{b->dI, (const float*)b->dF, (const float*)b->dFenv, b->nfrec, b->B, (const float*)q1, (const float*)q0, (const float*)qd0, (const float*)u, (float*)g_out, (float*)H_out, cycles, b->stage_cpt, b->pair_cull};
-    ok = ts_launch<false, float>(plan, (hipStream_t)stream, a);
-  } else {
-    DbgArgs<double> a{b->dI, (const double*)b->dF, (const double*)b->dFenv, b->nfrec, b->B, (const double*)q1, (const double*)q0, (const double*)qd0, (const double*)u, (double*)g_out, (double*)H_out, cycles, b->stage_cpt, b->pair_cull};
-    ok = ts_launch<false, double>(plan, (hipStream_t)stream, a);
-  }
+  const bool ok = by_real(b, [&](auto r) {
+    using R = decltype(r);
+    DbgArgs<R> a{b->dI, (const R*)b->dF, (const R*)b->dFenv, b->nfrec, b->B, (const R*)q1, (const R*)q0, (const R*)qd0, (const R*)u, (R*)g_out, (R*)H_out, cycles, b->stage_cpt, b->pair_cull};
+    return ts_launch<false, R>(plan, (hipStream_t)stream, a);
+  });
   if (!ok) return fail("no k_debug_eval instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   return 0;

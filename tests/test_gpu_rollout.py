@@ -344,3 +344,34 @@ def test_graphed_open_loop_episode_equals_the_eager_calls(name, adjoint):
                 assert torch.equal(ro[key], ro_e[key]), (name, k, key)
         if adjoint:
             assert torch.equal(du, du_e), (name, k)
+
+
+def test_captured_rollout_survives_growth_of_the_frame_pose_records(pusher_model):
+    """The per-frame pose records of an episode launch with a deferred tactile read-out grow only (csrc/tsim_hip.hip launch_forward).  A graph
+    captured from [reset; rollout of 2 frames] names the records it was captured with; an eager rollout of 4 frames then needs larger ones, and
+    the old ones are kept until the batch goes, not freed: the graph still replays to the eager bits of the 2 frames."""
+    from tactilesimulation_amd.host.batch import BatchSim
+    B, S, dt = 3, 2, torch.float32
+    q0_np, u_np, _ = push_workload(B, 4, seed=17)
+    q0 = torch.tensor(q0_np, device="cuda", dtype=dt)
+    u4 = torch.tensor(u_np, device="cuda", dtype=dt).transpose(0, 1).contiguous()        # [4, B, nu]
+    u2 = u4[:2].contiguous()
+    sim = BatchSim(pusher_model, B, dtype=dt, tape_capacity=0)
+    sim.reset(q0, None, False)
+    eager = sim.rollout(u2, S)                                # the warm-up: the records of 2 frames are allocated here
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        sim.reset(q0, None, False)
+        got = sim.rollout(u2, S)
+    sim.kernel_timing(True)
+    sim.rollout(u4, S)                                        # 4 frames: the records grow while the graph names the old ones
+    torch.cuda.synchronize()
+    assert sim.kernel_times()["k_taxels"][1] == 1             # the read-out was deferred to the taxel kernel, i.e. taken from per-frame records of 4 frames
+    sim.kernel_timing(False)
+    for k in ("q", "var", "tactile"):
+        got[k].fill_(7.0)
+    graph.replay()
+    torch.cuda.synchronize()
+    for k in ("q", "var", "tactile"):                         # (overwritten with 7 above: every entry equal means every entry was written again)
+        assert torch.equal(got[k], eager[k]), k

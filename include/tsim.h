@@ -237,13 +237,42 @@ int tsim_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, in
  * synchronisation; capturable.  A compiled-in model's batch runs the generic evaluation on its tape, as tsim_tangent_episode does.
  * Returns non-zero (tsim_last_error) and launches nothing for: a null batch; no tape recorded or a window longer than the tape; num_frames or
  * num_steps < 1; a BDF2 model (its transition acts on two states of history); a model whose block would not fit the 64 KB of LDS.
- * Out of scope: table columns and geometry as inputs; the tactile Jacobian (ndof_tactile x 2 ndof_r per frame and environment:
- * tsim_tangent_episode gives its action on a direction); BDF2; the B = 1 shim; the fused closed-loop tape. */
+ * Out of scope: table columns and geometry as inputs; BDF2; the B = 1 shim; the fused closed-loop tape.  (The tactile Jacobian, ndof_tactile x
+ * 2 ndof_r per frame and environment, has its own entry: tsim_tactile_jacobians below.) */
 int tsim_frame_jacobians(tsim_batch* b, int num_frames, int num_steps, void* A_out, void* B_out, void* Jvar_out, void* stream);
 /* Diagnostics: the static launch geometry of a tsim_frame_jacobians call, as tsim_tangent_launch_info reports a tangent call's: out[0] = LDS bytes
  * per block (the contexts and the slots' column blocks), out[1] = threads per block, out[2] = blocks PER FRAME, out[3] = lanes per environment:
  * the batch's, doubled until a block fits 64 KB; they do not depend on which outputs are asked for.  out = int32[4]. */
 int tsim_frame_jacobians_launch_info(const tsim_batch* b, int32_t* out);
+
+/* Per-frame tactile Jacobians (no reference counterpart): C_f = dtactile / dx, x = (q, qdot), of every MASKED frame of the newest num_frames *
+ * num_steps taped sub-steps, in ONE launch.  The window and tactile_slot are tsim_rollout's / tsim_tangent_episode's (DEVICE int32[num_frames],
+ * slot of frame f in Ct_out or < 0: frame not wanted; NULL: slot f).
+ *   Ct_out [num_masked][B][2 ndof_r][ndof_tactile]   the TRANSPOSE of C_f: row d is column d of C_f stored as one contiguous tactile frame (the
+ *                                                    layout of tsim_tangent_episode's dtac_out[d]); rows d < ndof_r are dtactile / dq_d, rows
+ *                                                    ndof_r + d are dtactile / dqdot_d.  Device memory, the batch's real type.
+ * It is large: 2 ndof_r * ndof_tactile reals per environment and masked frame (TactilePush, fp32: 21 840 bytes; D'Claw: 217 440 bytes).
+ * C_f is the Jacobian of the read-out map tac(q, qdot) at the frame's END state, q and qdot taken as independent variables.  So
+ * dtac_f = C_f dx_{f+1}, and with tsim_frame_jacobians' matrices C_f A_f and C_f B_f are the tactile response to the frame's start state and to
+ * its control; dtactile / du itself is zero.  Every loaded taxel emits, per column, A^T R_PA^T (Jx dx + Jv dxd - dth x F) with dx = dth x x + drho,
+ * dxd = dv + dw x x + wrel x dx and (dth, drho, dw, dv) the pair's record of the column's dof: tsim_tangent_episode's expression for a unit
+ * direction, without the parameter term.  At a stick / slip switch or a surface edge that is the one-sided derivative of the piece the taxel is
+ * on, as the adjoint and the tangent take it.  An unloaded taxel, and a sensor without primitives, give exact zero rows of C_f.  Parameters are
+ * the environment's row of tsim_set_env_tables, or the shared model's.  BDF2 and rotation-vector models are accepted: only the (q, qdot) of the
+ * frame's last tape record is read, nothing is solved.  A frame's bits depend neither on num_frames, nor on the mask, nor on the environment's
+ * position in the batch or the batch size.
+ * Read-only: the tape is not popped; the state, the carried adjoint, the cache and the pose records are untouched.  No allocation, no host
+ * synchronisation; capturable.  A compiled-in model's batch runs the generic evaluation on its tape, as tsim_tangent_episode does.
+ * Returns non-zero (tsim_last_error) and launches nothing for: a null batch or a null Ct_out; no tape recorded or a window longer than the tape;
+ * num_frames or num_steps < 1; a model without taxels; a model whose block would not fit the 64 KB of LDS; more than 2^31 - 1 blocks.  The mask is
+ * device memory, which this call does not read on the host: with no masked frame every block returns at once and nothing is written (the Python
+ * layer, which builds the mask, refuses such a call).
+ * Out of scope: table columns and geometry as inputs; the fused closed-loop tape; the B = 1 shim; products such as C^T W C. */
+int tsim_tactile_jacobians(tsim_batch* b, int num_frames, int num_steps, const int32_t* tactile_slot, void* Ct_out, void* stream);
+/* Diagnostics: the static launch geometry of a tsim_tactile_jacobians call, as tsim_frame_jacobians_launch_info reports: out[0] = LDS bytes per
+ * block (the contexts and the slots' record blocks), out[1] = threads per block, out[2] = blocks PER FRAME, out[3] = lanes per environment: the
+ * batch's, doubled until a block fits 64 KB.  out = int32[4]. */
+int tsim_tactile_jacobians_launch_info(const tsim_batch* b, int32_t* out);
 
 /* sim.backward() results df_dq0 / df_dqdot0                    envs/redmax_torch_functions.py:92-100
  * = the carried adjoint once the whole tape has been popped. [B][ndof_r] each. */

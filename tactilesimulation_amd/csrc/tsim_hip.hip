@@ -703,7 +703,7 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
   const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z || kernel == TS_K_CLOSED_BACKWARD_Z;
-  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || kernel == TS_K_FRAME_JACOBIAN || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || kernel == TS_K_FRAME_JACOBIAN || kernel == TS_K_TACTILE_JACOBIAN || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
   p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
@@ -718,6 +718,8 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   // the block's LDS does not hold that, fewer environments share a wavefront.  lds is the contexts'; frame_jacobian_plan adds the blocks,
   // launch_frame_jacobians multiplies the grid by the frames
   if (kernel == TS_K_FRAME_JACOBIAN) return slot_block_plan(b, p, ts_fj_slot_reals(b->nr, b->nu), 0).plan;
+  // the tactile Jacobians likewise: every slot holds a pair's per-dof records behind the contexts (tsim_tactile_jacobian.h)
+  if (kernel == TS_K_TACTILE_JACOBIAN) return slot_block_plan(b, p, ts_tj_slot_reals(b->nr), 0).plan;
   return p;
 }
 // the kernel arguments that come from the batch; each launch sets its own
@@ -1024,6 +1026,25 @@ static int launch_frame_jacobians(tsim_batch* b, int T, int S, void* A_out, void
   return 0;
 }
 
+// The per-frame tactile Jacobians of the masked frames of the newest T x S taped sub-steps (tsim_tactile_jacobians): one launch of the generic
+// k_tactile_jacobian, T x ceil(B / NS) blocks (a block of a frame that is not masked returns at once), whatever the batch's view, on the batch's
+// per-environment rows.  Reads the tape, writes the caller's buffer.  The plan: as frame_jacobian_plan
+static SlotPlan tactile_jacobian_plan(const tsim_batch* b) { return slot_block_plan(b, ts_plan(b, TS_K_TACTILE_JACOBIAN, false, 0), 0, ts_tj_slot_reals(b->nr)); }
+template <class R>
+static int launch_tactile_jacobians(tsim_batch* b, int T, int S, const int32_t* tac_slot, void* Ct_out, hipStream_t st) {
+  auto [plan, ctx_lds] = tactile_jacobian_plan(b);
+  if (plan.lds > TS_TAN_LDS_CAP) return fail("tactile_jacobians: a pair's per-dof records do not fit the block's LDS next to the context for this model");
+  if ((unsigned long long)plan.grid * (unsigned)T > 0x7fffffffull) return fail("tactile_jacobians: too many blocks");
+  TjArgs<R> a{};
+  pg_common<R>(b, a, T * S, T, S);      // a chunk is a frame
+  a.cull = b->pair_cull; a.xoff = (int)(ctx_lds / b->esz);
+  a.tac_slot = tac_slot; a.Ct_out = (R*)Ct_out;
+  plan.grid *= (unsigned)T;
+  if (!TsLaunch<void, false, R>::run(plan, st, a)) return fail("no k_tactile_jacobian instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // The checks the episode entry points share; who: the entry point, in front of the message.
 static int frames_positive(const std::string& who, int num_frames, int num_steps) {
   return num_frames <= 0 || num_steps <= 0 ? fail(who + ": num_frames and num_steps must be positive") : 0;
@@ -1141,6 +1162,10 @@ int tsim_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, in
 int tsim_frame_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
   if (!b || !out) return fail("frame_jacobians_launch_info: null argument");
   return plan_info(frame_jacobian_plan(b).plan, out);
+}
+int tsim_tactile_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
+  if (!b || !out) return fail("tactile_jacobians_launch_info: null argument");
+  return plan_info(tactile_jacobian_plan(b).plan, out);
 }
 int tsim_kernel_timing(tsim_batch* b, int enable) { b->kt_on = enable ? 1 : 0; return 0; }
 int tsim_kernel_times(tsim_batch* b, double* ms_sum, int32_t* launches) {
@@ -1446,6 +1471,17 @@ int tsim_frame_jacobians(tsim_batch* b, int num_frames, int num_steps, void* A_o
   if (!A_out && !B_out && !Jvar_out) return 0;
   TS_DEVICE(b);
   return by_real(b, [&](auto r) { return launch_frame_jacobians<decltype(r)>(b, num_frames, num_steps, A_out, B_out, Jvar_out, (hipStream_t)stream); });
+}
+
+int tsim_tactile_jacobians(tsim_batch* b, int num_frames, int num_steps, const int32_t* tactile_slot, void* Ct_out, void* stream) {
+  if (!b) return fail("tactile_jacobians: null batch");
+  if (b->ntax <= 0) return fail("tactile_jacobians: the model has no taxels");
+  if (!Ct_out) return fail("tactile_jacobians: null Ct_out");
+  if (!b->record || b->t_cur <= 0) return fail("tactile_jacobians: no tape recorded (reset(backward_flag=True), then a roll-out)");
+  long long n;
+  if (int rc = taped_window(b, "tactile_jacobians", num_frames, num_steps, &n)) return rc;
+  TS_DEVICE(b);
+  return by_real(b, [&](auto r) { return launch_tactile_jacobians<decltype(r)>(b, num_frames, num_steps, tactile_slot, Ct_out, (hipStream_t)stream); });
 }
 
 int tsim_get_adjoint(tsim_batch* b, void* df_dq0, void* df_dqd0, void* stream) {

@@ -300,3 +300,24 @@ def episode_transition(sim, num_frames, num_steps):
     follow.  BDF1 models only."""
     o = sim.frame_jacobians(num_frames, num_steps, want_A=True, want_B=True, want_var=False)
     return o["A"], o["B"]
+
+
+def episode_observation(sim, num_frames, num_steps, tactile_mask=None):
+    """The measurement map that goes with episode_transition: C [n_masked, B, ndof_tactile, 2 nr], C_f = dtactile / dx at the END state of masked
+    frame f, x = (q, qd) taken as independent variables — the tactile frame is what this simulator measures.  With (A, B) of episode_transition,
+    around the recorded roll-out and to first order:
+
+        dx_{f+1} = A_f dx_f + B_f du_f ,      dtac_f = C_f dx_{f+1}          (so C_f A_f, C_f B_f: the response to the frame's start state and control)
+
+    which is what a linearised (extended) Kalman filter around a recorded push takes: predict  x^- = A_f x^ + B_f du_f,  P^- = A_f P A_f^T + Q;
+    update with the innovation  y_f - C_f x^-  (y_f: measured minus recorded tactile frame); in information form  P^-1 = (P^-)^-1 + C_f^T R^-1 C_f,
+    P^-1 x^ = (P^-)^-1 x^- + C_f^T R^-1 y_f, with C_f^T R^-1 C_f only 2 nr x 2 nr.  An unloaded taxel's row is exactly zero; at a stick / slip
+    switch the row is the one-sided derivative of the piece the taxel is on.
+
+    The result is the transposed VIEW (no copy) of BatchSim.tactile_jacobians' Ct [n_masked, B, 2 nr, ndof_tactile], whose rows are contiguous
+    tactile frames: C.transpose(-1, -2) is contiguous, C is not.  Size: 2 nr * ndof_tactile reals per environment and masked frame — TactilePush
+    fp32 21 840 bytes (20 frames x 4096 environments: 1.79 GB), D'Claw 217 440 bytes (20 x 2048: 8.9 GB): mask the frames that are needed.
+
+    sim holds the tape of the newest num_frames x num_steps sub-steps.  One launch for every masked frame (include/tsim.h tsim_tactile_jacobians);
+    the tape, the state and the carried adjoint are left as they are.  BDF2 and rotation-vector models are accepted."""
+    return sim.tactile_jacobians(num_frames, num_steps, tactile_mask).transpose(-1, -2)

@@ -281,8 +281,25 @@ class BatchSim:
         capi.check(capi.lib().tsim_frame_jacobians(self._h, T, int(num_steps), _ptr(o.get("A")), _ptr(o.get("B")), _ptr(o.get("Jvar")), self._stream()))
         return o
 
+    def tactile_jacobians(self, num_frames, num_steps, tactile_mask=None):
+        """Per-frame tactile Jacobians of the newest num_frames env-steps (num_steps sub-steps each) in one launch (include/tsim.h
+        tsim_tactile_jacobians): Ct [n_masked, B, 2 ndof_r, ndof_tactile], the TRANSPOSE of C_f = dtactile / d(q, qd) at the frame's end state —
+        row d is column d of C_f as one tactile frame (rows < ndof_r: d/dq, the rest: d/dqd); functions.episode_observation gives the view
+        [.., ndof_tactile, 2 ndof_r].  tactile_mask (bool[T]) as in rollout: only the masked frames are computed and stored, and a mask without
+        a masked frame is refused.  An unloaded taxel gives exact zeros.  BDF2 and rotation-vector models are accepted.  The tape, the state and
+        the carried adjoint are left as they are; a frame's bits do not depend on num_frames, the mask or the batch size.
+        Size: 2 ndof_r * ndof_tactile reals per environment and masked frame — TactilePush fp32 21 840 bytes (20 frames x 4096 environments:
+        1.79 GB), D'Claw 217 440 bytes (20 x 2048: 8.9 GB): mask the frames that are needed."""
+        T = int(num_frames)
+        slots, nm = self._tactile_slots(T, tactile_mask)
+        if nm < 1:
+            raise ValueError("tactile_jacobians: the mask has no masked frame")
+        Ct = torch.empty((nm, self.B, 2 * self.ndof_r, self.ndof_tactile), device=self.device, dtype=self.dtype)
+        capi.check(capi.lib().tsim_tactile_jacobians(self._h, T, int(num_steps), _ptr(slots), _ptr(Ct), self._stream()))
+        return Ct
+
     def get_state(self):
-        q, qd = self.empty(self.ndof_r), self.empty(self.ndof_r)
+        q, qd =self.empty(self.ndof_r), self.empty(self.ndof_r)
         capi.check(capi.lib().tsim_get_state(self._h, _ptr(q), _ptr(qd), self._stream()))
         return q, qd
 
@@ -425,4 +442,11 @@ class BatchSim:
         may be wider than the batch's, where a block would not hold the 2 ndof_r + ndof_u columns of every slot"""
         out = (C.c_int32 * 4)()
         capi.check(capi.lib().tsim_frame_jacobians_launch_info(self._h, out))
+        return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}
+
+    def tactile_jacobians_launch_info(self):
+        """launch_info() of a tactile_jacobians call (include/tsim.h tsim_tactile_jacobians_launch_info): blocks PER FRAME; its lanes per
+        environment may be wider than the batch's, where a block would not hold a pair's 18 ndof_r record reals of every slot"""
+        out = (C.c_int32 * 4)()
+        capi.check(capi.lib().tsim_tactile_jacobians_launch_info(self._h, out))
         return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}

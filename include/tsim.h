@@ -237,8 +237,8 @@ int tsim_tangent_launch_info(const tsim_batch* b, int ndir, int with_dtables, in
  * synchronisation; capturable.  A compiled-in model's batch runs the generic evaluation on its tape, as tsim_tangent_episode does.
  * Returns non-zero (tsim_last_error) and launches nothing for: a null batch; no tape recorded or a window longer than the tape; num_frames or
  * num_steps < 1; a BDF2 model (its transition acts on two states of history); a model whose block would not fit the 64 KB of LDS.
- * Out of scope: table columns and geometry as inputs; BDF2; the B = 1 shim; the fused closed-loop tape.  (The tactile Jacobian, ndof_tactile x
- * 2 ndof_r per frame and environment, has its own entry: tsim_tactile_jacobians below.) */
+ * Out of scope: geometry as inputs; BDF2; the B = 1 shim; the fused closed-loop tape.  (The tactile Jacobian, ndof_tactile x 2 ndof_r per frame
+ * and environment, has its own entry: tsim_tactile_jacobians below; so have the contact-group table columns as inputs: tsim_param_jacobians.) */
 int tsim_frame_jacobians(tsim_batch* b, int num_frames, int num_steps, void* A_out, void* B_out, void* Jvar_out, void* stream);
 /* Diagnostics: the static launch geometry of a tsim_frame_jacobians call, as tsim_tangent_launch_info reports a tangent call's: out[0] = LDS bytes
  * per block (the contexts and the slots' column blocks), out[1] = threads per block, out[2] = blocks PER FRAME, out[3] = lanes per environment:
@@ -267,12 +267,52 @@ int tsim_frame_jacobians_launch_info(const tsim_batch* b, int32_t* out);
  * num_frames or num_steps < 1; a model without taxels; a model whose block would not fit the 64 KB of LDS; more than 2^31 - 1 blocks.  The mask is
  * device memory, which this call does not read on the host: with no masked frame every block returns at once and nothing is written (the Python
  * layer, which builds the mask, refuses such a call).
- * Out of scope: table columns and geometry as inputs; the fused closed-loop tape; the B = 1 shim; products such as C^T W C. */
+ * Out of scope: geometry as inputs; the fused closed-loop tape; the B = 1 shim; products such as C^T W C.  (The contact-group table columns as
+ * inputs, F_f = dtactile / dp, have their own entry: tsim_param_jacobians below.) */
 int tsim_tactile_jacobians(tsim_batch* b, int num_frames, int num_steps, const int32_t* tactile_slot, void* Ct_out, void* stream);
 /* Diagnostics: the static launch geometry of a tsim_tactile_jacobians call, as tsim_frame_jacobians_launch_info reports: out[0] = LDS bytes per
  * block (the contexts and the slots' record blocks), out[1] = threads per block, out[2] = blocks PER FRAME, out[3] = lanes per environment: the
  * batch's, doubled until a block fits 64 KB.  out = int32[4]. */
 int tsim_tactile_jacobians_launch_info(const tsim_batch* b, int32_t* out);
+
+/* Per-frame parameter Jacobians (no reference counterpart): the missing block of the local linearisation of a taped episode,
+ *     x_{f+1} ~ A_f x_f + B_f u_f + E_f p ,      tactile_f ~ C_f x_{f+1} + F_f p ,      x = (q, qdot),
+ * for every frame of the newest num_frames * num_steps taped sub-steps in ONE launch (A, B: tsim_frame_jacobians; C: tsim_tactile_jacobians).
+ * p is the environment's contact-group parameters, the columns tsim_set_param_grad differentiates: per contact pair and per tactile sensor
+ * kn kt mu damping, per dof its damping.
+ *   cols    HOST int32[ncols]: the table columns wanted in E (column indices of a tsim_table_size row; 1 .. TSIM_PARAM_JACOBIAN_MAX_COLS of
+ *           them, each once).  Read during the call and passed to the kernel by value; a caller who wants more columns launches again.
+ *   E_out   [num_frames][B][2 ndof_r][ncols]   E_f = dx_{f+1} / dp at fixed (x_f, u_f): rows (q, qdot) at the frame's end, column k = cols[k].
+ *   Ft_out  [num_masked][B][4][ndof_tactile]   F_f = dtactile / dp at fixed x_{f+1}, stored compactly: a taxel belongs to ONE sensor, so row k
+ *           (k = kn, kt, mu, damping) holds the derivative of every taxel w.r.t. field k of ITS OWN sensor, as one contiguous tactile frame (the
+ *           layout of Ct_out's rows).  The dense F_f (ndof_tactile x 4 nsensor) is that row scattered by sensor; pair and dof-damping columns
+ *           have no direct tactile term.  tactile_slot is tsim_tactile_jacobians' DEVICE mask (NULL: slot f); it is used for Ft_out only.
+ * Device memory, the batch's real type, row-major; either output may be NULL (not written), not both.
+ * E is tsim_tangent_episode's BDF1 recursion over the frame's sub-steps for unit dtables columns, every column starting at zero:
+ *     s_col = -K dq0_col + h M dqd0_col - dg/dp_col ,   H y = s ,   dq1 = dq0 + y ,   dqd1 = cv y
+ * with H the taped Newton matrix and K of the taped point, evaluated once for all columns, and M dqd0 the tangent pass's own product per column; the
+ * columns are solved eight per elimination of H.  dg/dp_col is the tangent pass's: for a pair column the pair's wrench derivative on every dof above its links, for a dof's damping
+ * qdot_j / ca on that dof.  Exact zeros: a sensor column (sensors do not enter the dynamics), a sensing-only pair, and a pair that is near in no
+ * sub-step of the frame, give an exactly zero column of E; an unloaded taxel and a sensor without primitives give exact zeros in Ft.
+ * With E_out NULL nothing is solved: only the frame's last record is evaluated, and BDF2 and rotation-vector models are accepted, as
+ * tsim_tactile_jacobians accepts them.  Parameters are the environment's row of tsim_set_env_tables, or the shared model's.  A column's bits
+ * depend neither on the other columns listed nor on its position in cols, nor on num_frames, on whether Ft_out is given, or on the batch size.
+ * Read-only: the tape is not popped; the state, the carried adjoint, the cache and the pose records are untouched.  No device copy, no
+ * allocation, no host synchronisation; capturable.  A compiled-in model's batch runs the generic evaluation on its tape.
+ * Returns non-zero (tsim_last_error) and launches nothing for: a null batch; both outputs NULL; E_out with ncols < 1 or >
+ * TSIM_PARAM_JACOBIAN_MAX_COLS or null cols; a column that is not a contact-group parameter (body-group columns, geometry, the float header); a
+ * column listed twice; Ft_out on a model without taxels; no tape recorded or a window longer than the tape; num_frames or num_steps < 1; E_out on a
+ * BDF2 model; a model whose block would not fit the 64 KB of LDS; more than 2^31 - 1 blocks.
+ * Scope: contact-group columns only.  Out of scope: the body groups (link inertia, motors, limits) and geometry as columns; the fused closed-loop
+ * tape; the B = 1 shim; more than TSIM_PARAM_JACOBIAN_MAX_COLS columns per launch. */
+enum { TSIM_PARAM_JACOBIAN_MAX_COLS = 32 };
+int tsim_param_jacobians(tsim_batch* b, int num_frames, int num_steps, int ncols, const int32_t* cols,
+                         const int32_t* tactile_slot, void* E_out, void* Ft_out, void* stream);
+/* Diagnostics: the static launch geometry of a tsim_param_jacobians call, as tsim_frame_jacobians_launch_info reports: out[0] = LDS bytes per
+ * block (the contexts and the slots' column blocks, sized for TSIM_PARAM_JACOBIAN_MAX_COLS columns), out[1] = threads per block, out[2] = blocks
+ * PER FRAME, out[3] = lanes per environment: the batch's, doubled until a block fits 64 KB; they depend neither on ncols nor on which outputs are
+ * asked for.  out = int32[4]. */
+int tsim_param_jacobians_launch_info(const tsim_batch* b, int32_t* out);
 
 /* sim.backward() results df_dq0 / df_dqdot0                    envs/redmax_torch_functions.py:92-100
  * = the carried adjoint once the whole tape has been popped. [B][ndof_r] each. */

@@ -703,7 +703,7 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
   const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z || kernel == TS_K_CLOSED_BACKWARD_Z;
-  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || kernel == TS_K_FRAME_JACOBIAN || kernel == TS_K_TACTILE_JACOBIAN || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || kernel == TS_K_FRAME_JACOBIAN || kernel == TS_K_TACTILE_JACOBIAN || kernel == TS_K_PARAM_JACOBIAN || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
   p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
@@ -720,6 +720,8 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   if (kernel == TS_K_FRAME_JACOBIAN) return slot_block_plan(b, p, ts_fj_slot_reals(b->nr, b->nu), 0).plan;
   // the tactile Jacobians likewise: every slot holds a pair's per-dof records behind the contexts (tsim_tactile_jacobian.h)
   if (kernel == TS_K_TACTILE_JACOBIAN) return slot_block_plan(b, p, ts_tj_slot_reals(b->nr), 0).plan;
+  // the parameter Jacobians likewise: every slot holds TS_PJ_MAX_COLS columns behind the contexts (tsim_param_jacobian.h), whatever the launch selects
+  if (kernel == TS_K_PARAM_JACOBIAN) return slot_block_plan(b, p, ts_pj_slot_reals(b->nr), 0).plan;
   return p;
 }
 // the kernel arguments that come from the batch; each launch sets its own
@@ -1045,6 +1047,28 @@ static int launch_tactile_jacobians(tsim_batch* b, int T, int S, const int32_t* 
   return 0;
 }
 
+// The per-frame parameter Jacobians over the newest T x S taped sub-steps (tsim_param_jacobians): one launch of the generic k_param_jacobian,
+// T x ceil(B / NS) blocks, whatever the batch's view, on the batch's per-environment rows.  Reads the tape, writes the caller's buffers.  The
+// plan: as frame_jacobian_plan, the slot's block sized for TS_PJ_MAX_COLS columns whatever the launch selects
+static SlotPlan param_jacobian_plan(const tsim_batch* b) { return slot_block_plan(b, ts_plan(b, TS_K_PARAM_JACOBIAN, false, 0), 0, ts_pj_slot_reals(b->nr)); }
+// cidx: the selected columns as compact indices (ts_pg_count order), ncols of them (0 without E_out); they travel by value in the arguments
+template <class R>
+static int launch_param_jacobians(tsim_batch* b, int T, int S, int ncols, const int* cidx, const int32_t* tac_slot, void* E_out, void* Ft_out, hipStream_t st) {
+  auto [plan, ctx_lds] = param_jacobian_plan(b);
+  if (plan.lds > TS_TAN_LDS_CAP) return fail("param_jacobians: the " + std::to_string((int)TS_PJ_MAX_COLS) + " columns of an environment do not fit the block's LDS for this model");
+  if ((unsigned long long)plan.grid * (unsigned)T > 0x7fffffffull) return fail("param_jacobians: too many blocks");
+  PjArgs<R> a{};
+  pg_common<R>(b, a, T * S, T, S);      // a chunk is a frame
+  a.cull = b->pair_cull; a.xoff = (int)(ctx_lds / b->esz);
+  a.ncols = ncols;
+  for (int k = 0; k < ncols; ++k) a.col[k] = cidx[k];
+  a.tac_slot = tac_slot; a.E_out = (R*)E_out; a.Ft_out = (R*)Ft_out;
+  plan.grid *= (unsigned)T;
+  if (!TsLaunch<void, false, R>::run(plan, st, a)) return fail("no k_param_jacobian instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // The checks the episode entry points share; who: the entry point, in front of the message.
 static int frames_positive(const std::string& who, int num_frames, int num_steps) {
   return num_frames <= 0 || num_steps <= 0 ? fail(who + ": num_frames and num_steps must be positive") : 0;
@@ -1166,6 +1190,10 @@ int tsim_frame_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
 int tsim_tactile_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
   if (!b || !out) return fail("tactile_jacobians_launch_info: null argument");
   return plan_info(tactile_jacobian_plan(b).plan, out);
+}
+int tsim_param_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
+  if (!b || !out) return fail("param_jacobians_launch_info: null argument");
+  return plan_info(param_jacobian_plan(b).plan, out);
 }
 int tsim_kernel_timing(tsim_batch* b, int enable) { b->kt_on = enable ? 1 : 0; return 0; }
 int tsim_kernel_times(tsim_batch* b, double* ms_sum, int32_t* launches) {
@@ -1482,6 +1510,44 @@ int tsim_tactile_jacobians(tsim_batch* b, int num_frames, int num_steps, const i
   if (int rc = taped_window(b, "tactile_jacobians", num_frames, num_steps, &n)) return rc;
   TS_DEVICE(b);
   return by_real(b, [&](auto r) { return launch_tactile_jacobians<decltype(r)>(b, num_frames, num_steps, tactile_slot, Ct_out, (hipStream_t)stream); });
+}
+
+// table column -> compact index in ts_pg_count order ([pair kn kt mu kd], [sensor kn kt mu kd], [dof damping]: launch_param_grad's segments), or -1
+static_assert((int)TS_PJ_MAX_COLS == (int)TSIM_PARAM_JACOBIAN_MAX_COLS, "tsim_param_jacobian.h and include/tsim.h disagree");
+static int contact_column_index(const tsim_batch* b, int col) {
+  const int npair = b->I[TSIM_IH_NPAIR], nsensor = b->I[TSIM_IH_NSENSOR];
+  const struct { int count, per, rec, col0, base; } seg[3] = {{npair, 4, TSIM_PF_SIZE, b->I[TSIM_IH_FOFF_PAIR] + TSIM_PF_KN, 0},
+                                                               {nsensor, 4, TSIM_SF_SIZE, b->I[TSIM_IH_FOFF_SENSOR] + TSIM_SF_KN, 4 * npair},
+                                                               {b->nr, 1, TSIM_DF_SIZE, b->I[TSIM_IH_FOFF_DOF] + TSIM_DF_DAMPING, 4 * npair + 4 * nsensor}};
+  for (const auto& s : seg) {
+    const int rel = col - s.col0;
+    if (rel < 0 || rel >= s.count * s.rec) continue;
+    if (rel % s.rec < s.per) return s.base + (rel / s.rec) * s.per + rel % s.rec;
+  }
+  return -1;
+}
+
+int tsim_param_jacobians(tsim_batch* b, int num_frames, int num_steps, int ncols, const int32_t* cols, const int32_t* tactile_slot, void* E_out, void* Ft_out, void* stream) {
+  if (!b) return fail("param_jacobians: null batch");
+  if (!E_out && !Ft_out) return fail("param_jacobians: E_out and Ft_out are both null");
+  int cidx[TS_PJ_MAX_COLS];
+  if (E_out) {
+    if (ncols < 1 || ncols > TSIM_PARAM_JACOBIAN_MAX_COLS) return fail("param_jacobians: ncols must be 1 .. " + std::to_string((int)TSIM_PARAM_JACOBIAN_MAX_COLS) + ", got " + std::to_string(ncols));
+    if (!cols) return fail("param_jacobians: null cols");
+    for (int k = 0; k < ncols; ++k) {
+      cidx[k] = contact_column_index(b, cols[k]);
+      if (cidx[k] < 0) return fail("param_jacobians: table column " + std::to_string(cols[k]) + " is not a contact-group parameter (pair or sensor kn kt mu damping, dof damping)");
+      for (int i = 0; i < k; ++i)
+        if (cidx[i] == cidx[k]) return fail("param_jacobians: table column " + std::to_string(cols[k]) + " is listed twice");
+    }
+  }
+  if (Ft_out && b->ntax <= 0) return fail("param_jacobians: Ft_out on a model without taxels");
+  if (!b->record || b->t_cur <= 0) return fail("param_jacobians: no tape recorded (reset(backward_flag=True), then a roll-out)");
+  long long n;
+  if (int rc = taped_window(b, "param_jacobians", num_frames, num_steps, &n)) return rc;
+  if (E_out && b->I[TSIM_IH_INTEGRATOR] == 2) return fail("param_jacobians: E_out on a BDF2 model (its transition acts on two states of history), which is out of scope");
+  TS_DEVICE(b);
+  return by_real(b, [&](auto r) { return launch_param_jacobians<decltype(r)>(b, num_frames, num_steps, E_out ? ncols : 0, cidx, tactile_slot, E_out, Ft_out, (hipStream_t)stream); });
 }
 
 int tsim_get_adjoint(tsim_batch* b, void* df_dq0, void* df_dqd0, void* stream) {

@@ -321,3 +321,43 @@ def episode_observation(sim, num_frames, num_steps, tactile_mask=None):
     sim holds the tape of the newest num_frames x num_steps sub-steps.  One launch for every masked frame (include/tsim.h tsim_tactile_jacobians);
     the tape, the state and the carried adjoint are left as they are.  BDF2 and rotation-vector models are accepted."""
     return sim.tactile_jacobians(num_frames, num_steps, tactile_mask).transpose(-1, -2)
+
+
+def episode_parameters(sim, num_frames, num_steps, cols, tactile_mask=None):
+    """The parameter block that completes episode_transition and episode_observation: (E, F) with E [T, B, 2 nr, ncols] and F [n_masked, B,
+    ndof_tactile, ncols], p the table columns `cols` (out of model.param_columns(): per contact pair and per tactile sensor kn kt mu damping, per
+    dof its damping), around the recorded roll-out and to first order:
+
+        dx_{f+1} = A_f dx_f + B_f du_f + E_f dp ,      dtac_f = C_f dx_{f+1} + F_f dp
+
+    E_f = dx_{f+1} / dp at fixed (x_f, u_f), F_f = dtactile / dp at fixed x_{f+1}.  What a joint state-and-parameter filter takes (augmented
+    state (x, p): [[A, E], [0, I]], [C | F]), and multiple-shooting or equation-error identification, where every frame's residual Jacobian
+    stands alone.  A sensor column is exactly zero in E (sensors do not enter the dynamics); F is non-zero only in a sensor column, and there only
+    on that sensor's taxels: it is scattered from BatchSim.param_jacobians' compact Ft.  F is None for a model without taxels.
+
+    sim holds the tape of the newest num_frames x num_steps sub-steps.  One launch per 32 columns (include/tsim.h tsim_param_jacobians); the tape,
+    the state and the carried adjoint are left as they are.  BDF1 models only."""
+    from .model import blob as B
+    cols = [int(c) for c in cols]
+    m, nmax = sim.model, sim.PARAM_JACOBIAN_MAX_COLS
+    want_F = sim.ndof_tactile > 0
+    E, Ft = [], None
+    for c0 in range(0, len(cols), nmax):
+        o = sim.param_jacobians(num_frames, num_steps, cols[c0:c0 + nmax], want_E=True, want_tactile=want_F and c0 == 0, tactile_mask=tactile_mask)
+        E.append(o["E"])
+        Ft = o.get("Ft", Ft)
+    E = torch.cat(E, -1) if E else torch.zeros((int(num_frames), sim.B, 2 * sim.ndof_r, 0), device=sim.device, dtype=sim.dtype)
+    if not want_F:
+        return E, None
+    if Ft is None:
+        Ft = sim.param_jacobians(num_frames, num_steps, (), want_E=False, want_tactile=True, tactile_mask=tactile_mask)["Ft"]
+    F = torch.zeros((Ft.shape[0], sim.B, sim.ndof_tactile, len(cols)), device=sim.device, dtype=sim.dtype)
+    at = {c: k for k, c in enumerate(cols)}
+    off, foff = int(m.I[B.TSIM_IH_OFF_SENSOR]), int(m.I[B.TSIM_IH_FOFF_SENSOR])
+    for s in range(int(m.I[B.TSIM_IH_NSENSOR])):
+        tx0, nt = (int(m.I[off + s * B.TSIM_SI_SIZE + i]) for i in (B.TSIM_SI_TAX0, B.TSIM_SI_NTAX))
+        for f in range(4):      # kn kt mu damping: Ft's rows
+            k = at.get(foff + s * B.TSIM_SF_SIZE + B.TSIM_SF_KN + f)
+            if k is not None:
+                F[:, :, 3 * tx0:3 * (tx0 + nt), k] = Ft[:, :, f, 3 * tx0:3 * (tx0 + nt)]
+    return E, F

@@ -298,6 +298,34 @@ class BatchSim:
         capi.check(capi.lib().tsim_tactile_jacobians(self._h, T, int(num_steps), _ptr(slots), _ptr(Ct), self._stream()))
         return Ct
 
+    PARAM_JACOBIAN_MAX_COLS = 32      # TSIM_PARAM_JACOBIAN_MAX_COLS of include/tsim.h
+
+    def param_jacobians(self, num_frames, num_steps, cols, want_E=True, want_tactile=False, tactile_mask=None):
+        """Per-frame parameter Jacobians of the newest num_frames env-steps (num_steps sub-steps each) in one launch (include/tsim.h
+        tsim_param_jacobians), with x = (q, qd) and p the environment's contact-group parameters: a dict of E [T, B, 2 ndof_r, len(cols)] =
+        dx_{f+1} / dp at fixed (x_f, u_f) (want_E; cols: 1 .. 32 table columns out of model.param_columns(), each once; BDF1 models only) and Ft
+        [n_masked, B, 4, ndof_tactile] = dtactile / dp at fixed x_{f+1} (want_tactile), stored compactly: row k is the derivative of every taxel
+        w.r.t. field k (kn, kt, mu, damping) of its OWN sensor; functions.episode_parameters scatters it to the dense F.  tactile_mask (bool[T]) as
+        in tactile_jacobians, for Ft only; a mask without a masked frame is refused.  Sensor columns, sensing-only pairs and pairs out of contact
+        give exactly zero columns of E; unloaded taxels exact zeros in Ft.  The tape, the state and the carried adjoint are left as they are; a
+        column's bits depend neither on the other columns nor on num_frames, want_tactile or the batch size."""
+        T = int(num_frames)
+        o = {}
+        ncols, carr = 0, None
+        if want_E:
+            cols = [int(x) for x in cols]
+            ncols = len(cols)
+            carr = (C.c_int32 * max(ncols, 1))(*cols)
+            o["E"] = torch.empty((T, self.B, 2 * self.ndof_r, ncols), device=self.device, dtype=self.dtype)
+        slots = None
+        if want_tactile:
+            slots, nm = self._tactile_slots(T, tactile_mask)
+            if nm < 1:
+                raise ValueError("param_jacobians: the mask has no masked frame")
+            o["Ft"] = torch.empty((nm, self.B, 4, self.ndof_tactile), device=self.device, dtype=self.dtype)
+        capi.check(capi.lib().tsim_param_jacobians(self._h, T, int(num_steps), ncols, carr, _ptr(slots), _ptr(o.get("E")), _ptr(o.get("Ft")), self._stream()))
+        return o
+
     def get_state(self):
         q, qd =self.empty(self.ndof_r), self.empty(self.ndof_r)
         capi.check(capi.lib().tsim_get_state(self._h, _ptr(q), _ptr(qd), self._stream()))
@@ -449,4 +477,12 @@ class BatchSim:
         environment may be wider than the batch's, where a block would not hold a pair's 18 ndof_r record reals of every slot"""
         out = (C.c_int32 * 4)()
         capi.check(capi.lib().tsim_tactile_jacobians_launch_info(self._h, out))
+        return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}
+
+    def param_jacobians_launch_info(self):
+        """launch_info() of a param_jacobians call (include/tsim.h tsim_param_jacobians_launch_info): blocks PER FRAME; its lanes per
+        environment may be wider than the batch's, where a block would not hold the 32 columns of every slot; they depend neither on the
+        columns selected nor on the outputs asked for"""
+        out = (C.c_int32 * 4)()
+        capi.check(capi.lib().tsim_param_jacobians_launch_info(self._h, out))
         return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}

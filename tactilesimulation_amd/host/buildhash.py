@@ -72,7 +72,8 @@ HIP_UNITS = [("tsim_hip.hip", []), ("tsim_static_pusher.hip", ["-ffinite-math-on
              ("tsim_tangent_closed.hip", []),                                                     # the tangent pass through the fused closed loop (k_closed_tangent, tsim_push_closed_tangent): generic flags, a unit of its own likewise
              ("tsim_frame_jacobian.hip", []),                                                     # the per-frame transition Jacobians (k_frame_jacobian, tsim_frame_jacobians): generic flags, a unit of its own likewise
              ("tsim_tactile_jacobian.hip", []),                                                   # the per-frame tactile Jacobians (k_tactile_jacobian, tsim_tactile_jacobians): generic flags, a unit of its own likewise
-             ("tsim_model.cpp", ["-ffp-contract=off"])]                                           # host only: the model loader (include/tsim_model.h); plain double arithmetic, no contraction
+             ("tsim_param_jacobian.hip", []),                                                     # the per-frame parameter Jacobians (k_param_jacobian, tsim_param_jacobians): generic flags, a unit of its own likewise
+             ("tsim_model.cpp", ["-ffp-contract=off"])]                                         # host only: the model loader (include/tsim_model.h); plain double arithmetic, no contraction
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC"]      # units that are not .hip: no device code
 
 

@@ -414,9 +414,15 @@ const char* tsim_kernel_variant(const tsim_batch* b);
  * the end of each frame; 1: after it, from the tape, by the frame-record pass — tsim_rollout launches of more than one frame on a fused compiled-in
  * model that record a tape and read the tactile frames out after the launch; 2: ... and the forward kernel was the instantiation that has this as a
  * compile-time constant (every option at its default).  The same results bit for bit (tests/test_gpu_frame_records.py); environment variable
- * TSIM_INKERNEL_FRAME_OUT=1 at creation: always 0. */
+ * TSIM_INKERNEL_FRAME_OUT=1 at creation: always 0.
+ * TSIM_OPT_FORWARD_SPLIT (read-only): 1 iff the newest forward launch went out as two — the heaviest eighth of its wavefronts (by the order the
+ * previous episode launch of the same length left) on the caller's stream, the others with their read-out on a side stream of the batch, which the
+ * caller's stream waits for before the call returns: the light environments' frames are read out while the heavy ones are still being simulated.
+ * Launches with TSIM_OPT_FRAME_RECORDS != 0 that have that order, a batch that is a multiple of the environments per wavefront, 64 blocks or more and
+ * no more than the device holds at once; never inside a stream capture.  The same results bit for bit (tests/test_gpu_forward_split.py);
+ * environment variable TSIM_NO_FORWARD_SPLIT=1 at creation: always 0. */
 enum { TSIM_OPT_PAIR_CULL = 1, TSIM_OPT_VALUE_TRIALS = 2, TSIM_OPT_TRIAL_HELPERS = 3, TSIM_OPT_VALUE_FIRST = 4, TSIM_OPT_CROSS_KINKS = 5, TSIM_OPT_EVAL_BUDGET = 6,
-       TSIM_OPT_ALL_DEFAULT = 7, TSIM_OPT_FRAME_RECORDS = 8 };
+       TSIM_OPT_ALL_DEFAULT = 7, TSIM_OPT_FRAME_RECORDS = 8, TSIM_OPT_FORWARD_SPLIT = 9 };
 int tsim_set_option(tsim_batch* b, int option, int value);
 int tsim_get_option(const tsim_batch* b, int option);
 

@@ -79,6 +79,12 @@ struct tsim_batch {
   int stage_cpt;                 // the contact-point arrays are staged in LDS with the shared tables
   int n_simd;                    // SIMDs of the device (CUs x 4)
   int last_frame_rec = 0;        // the newest forward launch left its frames' outputs to k_frame_records (1; 2: and ran k_forward_fr; tsim_get_option TSIM_OPT_FRAME_RECORDS)
+  // The forward launch split by LPT rank (launch_forward); all three null with TSIM_NO_FORWARD_SPLIT=1 at creation (or where they could not be
+  // created): one launch everywhere
+  hipStream_t split_st = nullptr;    // the side stream that carries the light wavefronts and their read-out
+  hipEvent_t split_fork = nullptr;   // recorded on the caller's stream before the heavy launch: the side stream waits for it
+  hipEvent_t split_join = nullptr;   // recorded on the side stream behind its last kernel: the caller's stream waits for it
+  int last_fwd_split = 0;        // the newest forward launch went out split (tsim_get_option TSIM_OPT_FORWARD_SPLIT)
   int value_trials = 2;          // line-search trials after this many rejected ones evaluate the residual only (0: off; tsim_set_option TSIM_OPT_VALUE_TRIALS; TSIM_VALUE_TRIALS=n at creation)
   int trial_helpers = 1;        // finished slots of a wavefront evaluate the next line-search trials of a slot that is still in one (tsim_set_option TSIM_OPT_TRIAL_HELPERS; TSIM_NO_TRIAL_HELPERS=1 at creation: off)
   int value_first = 1;           // launches without a tape: the first trial after a Newton step evaluates the residual only where the previous sub-step converged in one step (tsim_set_option TSIM_OPT_VALUE_FIRST; TSIM_NO_VALUE_FIRST=1 at creation: off)
@@ -123,6 +129,13 @@ struct tsim_batch {
   std::vector<hipEvent_t> kt_free;  // events to reuse
 };
 template <class F> static auto by_real(const tsim_batch* b, F&& f) { return by_dtype(b->dtype, f); }
+// the side stream and the events of the split forward launch go (on the batch's device; destroying a stream lets its work finish first)
+static void split_release(tsim_batch* b) {
+  if (b->split_st) (void)hipStreamDestroy(b->split_st);
+  if (b->split_fork) (void)hipEventDestroy(b->split_fork);
+  if (b->split_join) (void)hipEventDestroy(b->split_join);
+  b->split_st = nullptr; b->split_fork = b->split_join = nullptr;
+}
 
 // One timed launch: start event in the constructor, stop event in the destructor (nothing under stream capture: no events inside a graph).
 struct KtScope {

@@ -274,12 +274,14 @@ __global__ void __launch_bounds__(256) k_taxels(TaxArgs<R> a) {
 // record is all prologue (k_taxels above: ~3 us of dependent loads and two barriers for 130 taxels).  Here a block stages TXS_RPB records
 // at once — one cooperative copy, one barrier — and its threads then run over (record, taxel) items; consecutive items are consecutive
 // taxels of one record, so loads and the 12-byte stores stay contiguous.  Same taxel_eval, same tables: the same bits as k_taxels.
+// sub: the launch covers the environments order[e0 .. e0 + n) only — item g of its nrec = frames x n is frame g / n of the g % n-th of them —; the
+// records and the outputs keep their place, frame * B + environment.  (e0 = 0, n = B, no order: item g is record g, as ever.)
 enum { TXS_RPB = 16, TXS_MAXK = 8, TXS_MAXS = 4, TXS_MAX_TAXELS = 1024 };
 template <class R>
-__global__ void __launch_bounds__(256) k_taxels_small(TaxArgs<R> a, int nrec) {
+__global__ void __launch_bounds__(256) k_taxels_small(TaxArgs<R> a, int nrec, TsSubRange sub) {
   const int rec0 = blockIdx.x * TXS_RPB, nr_ = min((int)TXS_RPB, nrec - rec0);
   const int ntax = a.ntax, nsensor = a.nsensor, nspt = a.nspt;
-  __shared__ int sEnd[TXS_MAXS], sKb[TXS_MAXS], sNsp[TXS_MAXS], sPrim[TXS_MAXK], sPair[TXS_MAXK], sSlot[TXS_RPB];
+  __shared__ int sEnd[TXS_MAXS], sKb[TXS_MAXS], sNsp[TXS_MAXS], sPrim[TXS_MAXK], sPair[TXS_MAXK], sSlot[TXS_RPB], sEnv[TXS_RPB], sRec[TXS_RPB];
   __shared__ R sSf[TXS_RPB][TXS_MAXS * TSIM_SF_SIZE], sShape[TXS_RPB][TXS_MAXK * 4], sP[TXS_RPB][TXS_MAXK * TP_R_SIZE];
   __shared__ double sD[TXS_RPB][TXS_MAXK * TP_D_SIZE];
   __shared__ __attribute__((aligned(16))) R sC[TXS_RPB][TXS_MAXK * 4];
@@ -289,18 +291,22 @@ __global__ void __launch_bounds__(256) k_taxels_small(TaxArgs<R> a, int nrec) {
   const int* TT = a.I + a.tt_off;
   for (int i = threadIdx.x; i < nsensor; i += 256) { sEnd[i] = TT[3 * i]; sKb[i] = TT[3 * i + 1]; sNsp[i] = TT[3 * i + 2]; }
   for (int i = threadIdx.x; i < nspt; i += 256) { sPrim[i] = TT[3 * nsensor + 2 * i]; sPair[i] = TT[3 * nsensor + 2 * i + 1]; }
-  for (int i = threadIdx.x; i < nr_; i += 256) { const int fr = (rec0 + i) / a.B; sSlot[i] = a.tac_slot ? a.tac_slot[fr] : fr; }
-  for (int i = threadIdx.x; i < nr_ * nspt * TP_R_SIZE; i += 256) { const int r = i / (nspt * TP_R_SIZE), e = i % (nspt * TP_R_SIZE); sP[r][e] = a.poseR[(size_t)(rec0 + r) * nspt * TP_R_SIZE + e]; }
-  for (int i = threadIdx.x; i < nr_ * nspt * TP_D_SIZE; i += 256) { const int r = i / (nspt * TP_D_SIZE), e = i % (nspt * TP_D_SIZE); sD[r][e] = a.poseD[(size_t)(rec0 + r) * nspt * TP_D_SIZE + e]; }
+  for (int i = threadIdx.x; i < nr_; i += 256) {
+    const int fr = (rec0 + i) / sub.n, ei = sub.e0 + (rec0 + i) - fr * sub.n, env = sub.order ? sub.order[ei] : ei;
+    sSlot[i] = a.tac_slot ? a.tac_slot[fr] : fr; sEnv[i] = env; sRec[i] = fr * a.B + env;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nr_ * nspt * TP_R_SIZE; i += 256) { const int r = i / (nspt * TP_R_SIZE), e = i % (nspt * TP_R_SIZE); sP[r][e] = a.poseR[(size_t)sRec[r] * nspt * TP_R_SIZE + e]; }
+  for (int i = threadIdx.x; i < nr_ * nspt * TP_D_SIZE; i += 256) { const int r = i / (nspt * TP_D_SIZE), e = i % (nspt * TP_D_SIZE); sD[r][e] = a.poseD[(size_t)sRec[r] * nspt * TP_D_SIZE + e]; }
   for (int i = threadIdx.x; i < nr_ * nsensor * TSIM_SF_SIZE; i += 256) {
     const int r = i / (nsensor * TSIM_SF_SIZE), e = i % (nsensor * TSIM_SF_SIZE);
-    const R* F = a.Fenv ? a.Fenv + (size_t)((rec0 + r) % a.B) * a.fstride : a.F;
+    const R* F = a.Fenv ? a.Fenv + (size_t)sEnv[r] * a.fstride : a.F;
     sSf[r][e] = F[a.foff_sensor + e];
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nr_ * nspt * 4; i += 256) {
     const int r = i / (nspt * 4), e = i % (nspt * 4);
-    const R* F = a.Fenv ? a.Fenv + (size_t)((rec0 + r) % a.B) * a.fstride : a.F;
+    const R* F = a.Fenv ? a.Fenv + (size_t)sEnv[r] * a.fstride : a.F;
     sShape[r][e] = F[a.foff_pair + sPair[e >> 2] * TSIM_PF_SIZE + TSIM_PF_SHAPE + (e & 3)];
   }
   __syncthreads();
@@ -310,7 +316,7 @@ __global__ void __launch_bounds__(256) k_taxels_small(TaxArgs<R> a, int nrec) {
     const int r = item / ntax, t = item - r * ntax;
     const int tslot = sSlot[r];
     if (tslot < 0) continue;
-    R* out = a.tac_out + ((size_t)tslot * a.B + (rec0 + r) % a.B) * 3 * ntax;
+    R* out = a.tac_out + ((size_t)tslot * a.B + sEnv[r]) * 3 * ntax;
     taxel_eval<R>(t, mk3<R>(sX[t], sX[t + ntax], sX[t + 2 * ntax]), nsensor, sEnd, sKb, sNsp, sPrim, sSf[r], sShape[r], sP[r], sD[r], sC[r], tax, ntax, out);
   }
 }
@@ -756,21 +762,28 @@ static bool pose_emit(tsim_batch* b, hipStream_t st) {
 // holds at once (occupancy x CUs), each with a slice long enough to cover the batch; never less than 256 taxels per block, so the
 // single environment of test_sim_speed.py still spreads its 40 000 taxels over 157 blocks.
 static bool taxels_supported(const tsim_batch* b) { return b->ntax > 0 && b->nspt > 0 && b->nspt <= TX_MAXK && b->I[TSIM_IH_NSENSOR] <= TX_MAXS; }
+// the launch is k_taxels_small's: many records of a small pad
+static bool taxels_small(const tsim_batch* b, long long nrec) {
+  return nrec >= 4 * TXS_RPB && b->ntax <= TXS_MAX_TAXELS && b->nspt <= TXS_MAXK && b->I[TSIM_IH_NSENSOR] <= TXS_MAXS && !b->ab_taxels_per_record;
+}
+// sub: the environments the launch covers (k_taxels_small only; null: all of them)
 template <class R>
-static int launch_taxels(tsim_batch* b, const void* poseR, const double* poseD, int frames, const int32_t* tac_slot, void* tac_out, hipStream_t st) {
+static int launch_taxels(tsim_batch* b, const void* poseR, const double* poseD, int frames, const int32_t* tac_slot, void* tac_out, hipStream_t st, const TsSubRange* sub = nullptr) {
   if (b->tax_slots == 0) {
     int per_cu = 0;
     const hipError_t e_ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_taxels<R>, 256, 0);
     b->tax_slots = (e_ == hipSuccess && per_cu > 0 ? per_cu : 4) * (b->n_simd / 4);
   }
-  const long long nrec = (long long)frames * b->B;
-  if (nrec >= 4 * TXS_RPB && b->ntax <= TXS_MAX_TAXELS && b->nspt <= TXS_MAXK && b->I[TSIM_IH_NSENSOR] <= TXS_MAXS && !b->ab_taxels_per_record) {
+  const TsSubRange all{nullptr, 0, b->B};
+  const long long nrec = (long long)frames * (sub ? sub->n : b->B);
+  if (taxels_small(b, nrec)) {
     TaxArgs<R> t{b->dI, (const R*)b->dF, (const R*)b->dFenv, b->nfrec, (const R*)poseR, poseD, b->nspt, (R*)tac_out, 0, b->B, tac_slot,
                  b->ntax, b->I[TSIM_IH_NSENSOR], b->I[TSIM_IH_FOFF_SENSOR], b->I[TSIM_IH_FOFF_PAIR], b->I[TSIM_IH_FOFF_TAXEL], b->tt_off};
-    hipLaunchKernelGGL(k_taxels_small<R>, dim3((unsigned)((nrec + TXS_RPB - 1) / TXS_RPB)), dim3(256), 0, st, t, (int)nrec);
+    hipLaunchKernelGGL(k_taxels_small<R>, dim3((unsigned)((nrec + TXS_RPB - 1) / TXS_RPB)), dim3(256), 0, st, t, (int)nrec, sub ? *sub : all);
     HIPCHK(hipGetLastError());
     return 0;
   }
+  if (sub) return fail("launch_taxels: a sub-range of the environments is k_taxels_small's");
   const int per_env = (int)std::max<long long>(1, std::min<long long>(b->tax_slots / nrec, (b->ntax + 255) / 256));
   const int slice = ((b->ntax + per_env - 1) / per_env + 255) / 256 * 256;
   const dim3 tgrid((unsigned)nrec, (b->ntax + slice - 1) / slice);
@@ -827,19 +840,74 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   a.frame_rec = frame_rec ? 1 : 0;
   plan.frame_rec = frame_rec;
   b->last_frame_rec = !frame_rec ? 0 : (plan.frame_rec && plan.default_opts) ? 2 : 1;
-  { KtScope kt_(b, TSIM_KT_FORWARD, st); if (!ts_launch<false, R>(plan, st, a)) return fail("no k_forward instantiation for the launch plan"); }
-  HIPCHK(hipGetLastError());
-  if (defer) {
-    KtScope kt_(b, TSIM_KT_TAXELS, st);
-    if (frame_rec) {
-      // about one block per SIMD: the blocks of a chunk cover the environments, the chunks the frames
-      TsPlan p = fr_plan;
-      const int nblk = (int)p.grid, chunks = std::max(1, std::min(nframes, b->n_simd / std::max(nblk, 1))), fpc = (nframes + chunks - 1) / chunks;
-      p.grid = (unsigned)(nblk * ((nframes + fpc - 1) / fpc));
-      if (!ts_launch<false, R>(p, st, a, fpc)) return fail("no k_frame_records instantiation for the launch plan");
+  // k_frame_records over the environments of sub, on stream s — about one block per SIMD: the blocks of a chunk cover the environments, the chunks the frames
+  const int ns_ = TS_WAVE / plan.lpe;
+  auto frame_records = [&](hipStream_t s, const TsSubRange& sub) {
+    TsPlan p = fr_plan;
+    const int nblk = (sub.n + ns_ - 1) / ns_, chunks = std::max(1, std::min(nframes, b->n_simd / std::max(nblk, 1))), fpc = (nframes + chunks - 1) / chunks;
+    p.grid = (unsigned)(nblk * ((nframes + fpc - 1) / fpc));
+    return ts_launch<false, R>(p, s, a, fpc, sub);
+  };
+  // The launch split by LPT rank.  Every wavefront of such a launch is resident at once, one per SIMD, and the launch lasts as long as its heaviest
+  // environment's chain of evaluations — while most SIMDs have run out of work long before (profiles/r27_forward_split.md).  The read-out side needs
+  // only the tape records of the environments it reads, so the launch goes out as two: the wavefronts [0, wh) — under the episode order's deal wavefront
+  // w holds the w-th heaviest environment (k_order_by_evals) — on the caller's stream, the others on the batch's side stream, each followed by the
+  // read-out of ITS environments; the light group's read-out then runs on the SIMDs its forward kernel has left, under the heavy group's tail.  The
+  // same kernels on the same inputs, environment by environment: the same bits.  The caller's stream waits for the side stream before anything else
+  // is put on it (the next order is computed from both groups' evaluation counts), so the caller sees one stream as ever.
+  // Not inside a capture (no parallel branches in a captured graph), nor without the episode order, nor where the wavefronts are not all resident.
+  const int nblk_f = (int)plan.grid, wh = std::max(1, nblk_f / 8);
+  const bool split = frame_rec && b->split_st && a.order && a.order == (const int*)b->order_ep && b->B % ns_ == 0 && nblk_f <= b->n_simd && nblk_f >= 64 &&
+                     taxels_small(b, (long long)nframes * wh * ns_) && !capturing(st);
+  b->last_fwd_split = split ? 1 : 0;
+  if (split) {
+    const TsSubRange heavy{a.order, 0, wh * ns_}, light{a.order, wh * ns_, b->B - wh * ns_};
+    auto forward = [&](hipStream_t s, unsigned grid, const FwdArgs<R>& fa) -> int {
+      TsPlan p = plan; p.grid = grid;
+      if (!ts_launch<false, R>(p, s, fa)) return fail("no k_forward instantiation for the launch plan");
       HIPCHK(hipGetLastError());
+      return 0;
+    };
+    auto read_out = [&](hipStream_t s, const TsSubRange& sub) -> int {      // one group's frames, on the stream of its forward kernel
+      if (!frame_records(s, sub)) return fail("no k_frame_records instantiation for the launch plan");
+      HIPCHK(hipGetLastError());
+      return launch_taxels<R>(b, b->fposeR, b->fposeD, nframes, tac_slot, tac_out, s, &sub);
+    };
+    int rc;
+    {
+      KtScope kt_(b, TSIM_KT_FORWARD, st);
+      HIPCHK(hipEventRecord(b->split_fork, st));      // (nothing is on the side stream yet: the fork may leave directly)
+      HIPCHK(hipStreamWaitEvent(b->split_st, b->split_fork, 0));
+      rc = forward(st, (unsigned)wh, a);
     }
-    if (launch_taxels<R>(b, b->fposeR, b->fposeD, nframes, tac_slot, tac_out, st)) return 1;
+    // From the side stream's first launch on the join is never skipped: whatever fails below, the caller's stream waits for what did get onto the
+    // side stream before the error is returned
+    if (!rc) {
+      FwdArgs<R> al = a; al.order = a.order + light.e0;      // (a.B stays the stride of the tape and of the outputs)
+      rc = forward(b->split_st, (unsigned)(nblk_f - wh), al);
+    }
+    if (!rc) rc = read_out(b->split_st, light);
+    const hipError_t e_rec = hipEventRecord(b->split_join, b->split_st);
+    hipError_t e_wait;
+    {
+      KtScope kt_(b, TSIM_KT_TAXELS, st);
+      if (!rc) rc = read_out(st, heavy);
+      e_wait = e_rec == hipSuccess ? hipStreamWaitEvent(st, b->split_join, 0) : hipStreamSynchronize(b->split_st);
+    }
+    if (rc) return rc;
+    HIPCHK(e_rec);
+    HIPCHK(e_wait);
+  } else {
+    { KtScope kt_(b, TSIM_KT_FORWARD, st); if (!ts_launch<false, R>(plan, st, a)) return fail("no k_forward instantiation for the launch plan"); }
+    HIPCHK(hipGetLastError());
+    if (defer) {
+      KtScope kt_(b, TSIM_KT_TAXELS, st);
+      if (frame_rec) {
+        if (!frame_records(st, TsSubRange{nullptr, 0, b->B})) return fail("no k_frame_records instantiation for the launch plan");
+        HIPCHK(hipGetLastError());
+      }
+      if (launch_taxels<R>(b, b->fposeR, b->fposeD, nframes, tac_slot, tac_out, st)) return 1;
+    }
   }
   b->pose_valid = emit ? 1 : 0;
   if (b->B >= 256) {
@@ -1153,6 +1221,15 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   if (hipMemset(b->tape, 0, tape_bytes) != hipSuccess || hipMemset(b->lamq, 0, (size_t)2 * B * nr * b->esz) != hipSuccess ||
       hipMemset(b->lamv, 0, (size_t)2 * B * nr * b->esz) != hipSuccess) { tsim_batch_destroy(b); return fail("hipMemset failed"); }
   if (upload_model(b, nullptr)) { tsim_batch_destroy(b); return 1; }
+  // the side stream of the split forward launch (launch_forward; a split has 64 blocks or more).  Non-blocking: it is ordered against the caller's
+  // stream by its two events alone — the caller's may be the null stream, which every blocking stream waits for
+  if (B >= 64 && !getenv("TSIM_NO_FORWARD_SPLIT")) {
+    if (hipStreamCreateWithFlags(&b->split_st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&b->split_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&b->split_join, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      split_release(b);
+    }
+  }
   *out = b;
   return 0;
 }
@@ -1165,6 +1242,7 @@ void tsim_batch_destroy(tsim_batch* b) {
   for (void* p : b->retired) (void)hipFree(p);
   for (auto& k : b->kt) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
   for (hipEvent_t e : b->kt_free) (void)hipEventDestroy(e);
+  split_release(b);
   (void)hipFree(b->tape);
   delete b;      // the buffers the batch owns (DevBuf) go with it, on the batch's device: guard_ is still in scope
 }
@@ -1244,6 +1322,7 @@ int tsim_get_option(const tsim_batch* b, int option) {
   if (option == TSIM_OPT_EVAL_BUDGET) return b->eval_budget;
   if (option == TSIM_OPT_ALL_DEFAULT) return default_options(b) ? 1 : 0;
   if (option == TSIM_OPT_FRAME_RECORDS) return b->last_frame_rec;
+  if (option == TSIM_OPT_FORWARD_SPLIT) return b->last_fwd_split;
   return -1;
 }
 int tsim_set_solver_options(tsim_batch* b, int cross_kinks, int eval_budget) {

@@ -93,6 +93,8 @@ __device__ __forceinline__ void readout(const Ctx<R>& c, int lane, int env, bool
 __device__ __forceinline__ float ts_trial_point(float base, float alpha, float dq) { return __builtin_fmaf(alpha, dq, base); }
 __device__ __forceinline__ double ts_trial_point(double base, double alpha, double dq) { return __builtin_fma(alpha, dq, base); }
 enum { TP_R_SIZE = 18, TP_D_SIZE = 12 };      // pose record of a (sensor, primitive) combination: R part, double part (k_readout)
+// the environments a read-out launch covers: order[e0 .. e0 + n) of a block -> environment map, or e0 .. e0 + n themselves (order null)
+struct TsSubRange { const int* order; int e0, n; };
 template <class R> struct FwdArgs {
   const int* I; const R* F; const R* Fenv; int fstride;
   int B, nsub, record, t0;
@@ -609,20 +611,23 @@ __global__ void TS_KLB k_forward_fr(FwdArgs<R> a) { ts_forward<R, NRM, false, LP
 // accelerations enter no output: zero here, as in k_readout) — so q, qd, the variables and the frame's pose records are functions of data that is in
 // memory anyway, and ts_frame_outputs gives them the bits the in-kernel frame end gives them.  In k_forward that code runs on the launch's critical
 // wavefront, once per slot and frame with the other slots masked; here every SIMD of the device takes part.  Same 16 / 32 / 64 lanes per environment
-// and the same LDS layout as the forward launch; a slot keeps ITS environment (environment index = slot index: k_forward's order does not apply)
+// and the same LDS layout as the forward launch; a slot keeps ITS environment (slot i of the launch's range: k_forward's wavefront deal does not matter here)
 // and walks a.nframes in chunks of fpc frames (blockIdx.x / blocks-per-chunk: the chunk), so the model tables — per environment with
 // tsim_set_env_tables — are staged once per block, not once per record.
 // (One wavefront per SIMD, as the forward launch: its LDS footprint allows no more, and without the attribute this compiler's register allocator crashes on the kernel.)
+// sub: the launch covers the environments order[e0 .. e0 + n) only (a forward launch split by LPT rank reads each group out behind its own forward
+// kernel, tsim_hip.hip launch_forward); the records keep their place, frame * B + environment.  No order: environments e0 .. e0 + n themselves.
 template <class R, int LPE, class MS>
-__global__ void TS_KLB k_frame_records(FwdArgs<R> a, int fpc) {
+__global__ void TS_KLB k_frame_records(FwdArgs<R> a, int fpc, TsSubRange sub) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   R* lds = reinterpret_cast<R*>(smem_raw);
   constexpr int NS = TS_WAVE / LPE;
   const int slot = threadIdx.x / LPE, lane = threadIdx.x % LPE;
-  const int nblk = (a.B + NS - 1) / NS, chunk = blockIdx.x / nblk;
+  const int nblk = (sub.n + NS - 1) / NS, chunk = blockIdx.x / nblk;
   const int eidx = (blockIdx.x - chunk * nblk) * NS + slot;
-  const bool valid = eidx < a.B;
-  const int env = min(eidx, a.B - 1);
+  const bool valid = eidx < sub.n;
+  const int ei = sub.e0 + min(eidx, sub.n - 1);
+  const int env = sub.order ? sub.order[ei] : ei;
   Ctx<R> c; ctx_init<R, MS>(c, a.I, a.F, lds, NS, slot, lane, LPE, false, a.Fenv ? a.Fenv + (size_t)env * a.fstride : nullptr);      // (no contact points: nothing here reads them)
   const int nr = c.nr, REC = ts_rec(nr, c.nu, (int)sizeof(R), a.tk);
   init_world(c, lane, LPE);

@@ -87,7 +87,7 @@ template <class MS, bool POLICY, class R> struct TsLaunch {
     return p.nrm == 8 ? lanes(TsInt<8>(), TsBool<false>()) : p.nrm == 16 && lanes(TsInt<16>(), TsBool<false>());
   }
   static bool run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a);
-  static bool run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a, int fpc);      // k_frame_records (TS_K_FRAME_RECORDS): fpc frames per block
+  static bool run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a, int fpc, TsSubRange sub);      // k_frame_records (TS_K_FRAME_RECORDS): fpc frames per block, the environments of sub
   static bool run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave = nullptr);      // zsave: k_backward_z (TS_K_BACKWARD_Z), k_closed_backward_z
   static bool run_closed_z(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave);      // TS_K_CLOSED_BACKWARD_Z; run() hands it over (a member of its own: the generic view's is instantiated in tsim_closed_backward_z.hip)
   static bool run(const TsPlan& p, hipStream_t st, const DbgArgs<R>& a);
@@ -113,9 +113,9 @@ template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(cons
     hipLaunchKernelGGL((k_forward<R, nrm, expj, lpe, POLICY, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a);
   });
 }
-template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a, int fpc) {
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const FwdArgs<R>& a, int fpc, TsSubRange sub) {
   if constexpr (!POLICY && ts_static_fused<MS, R>())
-    return shape<TS_K_FRAME_RECORDS>(p, [&](auto, auto, auto lpe) { hipLaunchKernelGGL((k_frame_records<R, lpe, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a, fpc); });
+    return shape<TS_K_FRAME_RECORDS>(p, [&](auto, auto, auto lpe) { hipLaunchKernelGGL((k_frame_records<R, lpe, MS>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a, fpc, sub); });
   else return false;
 }
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const BwdArgs<R>& a, R* zsave) {

@@ -162,7 +162,7 @@ def kernel_name(kernel, dtype, nr, has_exp, lanes, variant, policy=False, defaul
     # k_frame_records, the pass that writes the frames' outputs from the tape, at every shape the view's k_forward has; k_forward_fr, the forward
     # kernel with that switch and every option's default as constants, where the TsDefaultOpts<> twin is (fp32, 16 lanes)
     if kernel == "k_frame_records":
-        return ("_Z15k_frame_recordsI%sLi%dE%sEv7FwdArgsIT_Ei" % (r[0], lpe, ms[0]), "k_frame_records<%s, LPE=%d, %s>" % (r[1], lpe, ms[1]))
+        return ("_Z15k_frame_recordsI%sLi%dE%sEv7FwdArgsIT_Ei10TsSubRange" % (r[0], lpe, ms[0]), "k_frame_records<%s, LPE=%d, %s>" % (r[1], lpe, ms[1]))
     if kernel == "k_forward_fr":
         return ("_Z12k_forward_frI%sLi%dELi%dE%sEv7FwdArgsIT_E" % (r[0], nrm, lpe, ms[0]), "k_forward_fr<%s, NRM=%d, LPE=%d, %s>" % (r[1], nrm, lpe, ms[1]))
     # the closed-loop adjoint that also saves z (csrc/tsim_kernels.h k_closed_backward_z; FusedPushEpisode.backward with a table-gradient buffer set): no

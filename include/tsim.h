@@ -420,9 +420,15 @@ const char* tsim_kernel_variant(const tsim_batch* b);
  * caller's stream waits for before the call returns: the light environments' frames are read out while the heavy ones are still being simulated.
  * Launches with TSIM_OPT_FRAME_RECORDS != 0 that have that order, a batch that is a multiple of the environments per wavefront, 64 blocks or more and
  * no more than the device holds at once; never inside a stream capture.  The same results bit for bit (tests/test_gpu_forward_split.py);
- * environment variable TSIM_NO_FORWARD_SPLIT=1 at creation: always 0. */
+ * environment variable TSIM_NO_FORWARD_SPLIT=1 at creation: always 0.
+ * TSIM_OPT_PREDICTOR_HELPERS (default 1; environment variable TSIM_NO_PREDICTOR_HELPERS=1 at creation: 0; nothing without TSIM_OPT_TRIAL_HELPERS)  most
+ * sub-steps are two rounds, the evaluation at the predictor and the one at the trial point that is committed, and the next sub-step's predictor follows
+ * from that trial point alone.  A slot whose own environment is finished evaluates it in the same round; if the trial is committed, its environment
+ * starts the next sub-step from that evaluation: one round per sub-step while a finished slot shares the wavefront.  Fused compiled-in BDF1 models,
+ * free-running launches that record a tape.  Exact, as TSIM_OPT_TRIAL_HELPERS is (tests/test_gpu_predictor_helpers.py); tsim_last_helper_trials also
+ * counts the predictors taken over.  It is no part of TSIM_OPT_ALL_DEFAULT: the instantiations read it at run time. */
 enum { TSIM_OPT_PAIR_CULL = 1, TSIM_OPT_VALUE_TRIALS = 2, TSIM_OPT_TRIAL_HELPERS = 3, TSIM_OPT_VALUE_FIRST = 4, TSIM_OPT_CROSS_KINKS = 5, TSIM_OPT_EVAL_BUDGET = 6,
-       TSIM_OPT_ALL_DEFAULT = 7, TSIM_OPT_FRAME_RECORDS = 8, TSIM_OPT_FORWARD_SPLIT = 9 };
+       TSIM_OPT_ALL_DEFAULT = 7, TSIM_OPT_FRAME_RECORDS = 8, TSIM_OPT_FORWARD_SPLIT = 9, TSIM_OPT_PREDICTOR_HELPERS = 10 };
 int tsim_set_option(tsim_batch* b, int option, int value);
 int tsim_get_option(const tsim_batch* b, int option);
 

@@ -86,6 +86,7 @@ struct tsim_batch {
   hipEvent_t split_join = nullptr;   // recorded on the side stream behind its last kernel: the caller's stream waits for it
   int last_fwd_split = 0;        // the newest forward launch went out split (tsim_get_option TSIM_OPT_FORWARD_SPLIT)
   int value_trials = 2;          // line-search trials after this many rejected ones evaluate the residual only (0: off; tsim_set_option TSIM_OPT_VALUE_TRIALS; TSIM_VALUE_TRIALS=n at creation)
+  int pred_helpers = 1;         // ... and the predictor of the next sub-step of a slot whose evaluation may end its current one (tsim_set_option TSIM_OPT_PREDICTOR_HELPERS; TSIM_NO_PREDICTOR_HELPERS=1 at creation: off; nothing without trial_helpers)
   int trial_helpers = 1;        // finished slots of a wavefront evaluate the next line-search trials of a slot that is still in one (tsim_set_option TSIM_OPT_TRIAL_HELPERS; TSIM_NO_TRIAL_HELPERS=1 at creation: off)
   int value_first = 1;           // launches without a tape: the first trial after a Newton step evaluates the residual only where the previous sub-step converged in one step (tsim_set_option TSIM_OPT_VALUE_FIRST; TSIM_NO_VALUE_FIRST=1 at creation: off)
   // A/B switches of the environment, read ONCE at creation (launches are on the host-bound path of the per-step collectors):

@@ -732,14 +732,18 @@ template <class MS, class R> constexpr bool ts_static_fused() {
 // tang (wave-uniform, default true): false = the VALUES only — q, qd, qa, the link state and g; no tangent, no H (c.H keeps what it held).  Every
 // number it does compute is computed exactly as the full evaluation computes it.  k_forward asks for it when no environment of the wavefront
 // needs a Newton matrix from this round: line-search trials deep in a backtracking (only ||g|| decides them), finished slots.
+// The velocity and the double position of the point at increment d over the predictor, one expression each wherever they are formed: evaluate() and a
+// slot of k_forward that forms ANOTHER slot's point ahead of it (predictor helpers, tsim_kernels.h) must arrive at the same bits
+template <class R> __device__ __forceinline__ R ts_point_qd(R qdp, R cv, R d) { return qdp + cv * d; }
+template <class R> __device__ __forceinline__ double ts_point_qD(double qpD, R d) { return qpD + (double)d; }
 template <class R, int NRM, bool EXPJ, int LPE, class MS = void>
 __device__ __forceinline__ void evaluate(const Ctx<R>& c, int lane, R sq, R sv, R sa, bool tang = true) {
   if (lane < c.nr) {
     const R d = c.dl[lane];
-    c.qd[lane] = c.qdp[lane] + c.cv * d;
+    c.qd[lane] = ts_point_qd(c.qdp[lane], c.cv, d);
     c.qa[lane] = c.ca * d;
     c.q[lane] = c.qp[lane] + d;
-    c.qD[lane] = c.qpD[lane] + (double)d;
+    c.qD[lane] = ts_point_qD(c.qpD[lane], d);
   }
   TS_SYNC();
   TS_STAMP(c);

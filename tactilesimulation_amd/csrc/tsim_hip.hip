@@ -801,6 +801,7 @@ static int launch_forward(tsim_batch* b, const void* u, int nframes, const int32
   a.q_out = (R*)q_out; a.qd_out = (R*)qd_out; a.var_out = (R*)var_out; a.tac_out = (R*)tac_out; a.status = status;
   a.order = (b->B >= 256 && nframes == 1 && b->order_valid) ? (const int*)b->order : (b->B >= 256 && nframes > 1 && b->order_ep_n == nframes * nsub && !b->ab_no_episode_lpt) ? (const int*)b->order_ep : nullptr;
   a.vo_first = b->value_first; a.helpers = b->trial_helpers; a.helped = b->helped;
+  a.pred_helpers = b->trial_helpers && b->pred_helpers;      // (only where the trial helpers are; the kernel: only in free-running launches that record a tape, k_forward)
   const bool emit = pose_emit(b, st);
   a.nspt = b->nspt;
   if (emit) { a.poseR = (R*)b->poseR; a.poseD = b->poseD; }
@@ -1188,6 +1189,7 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   b->pair_cull = getenv("TSIM_NO_PAIR_CULL") ? 0 : 1;
   b->no_static = getenv("TSIM_NO_STATIC") != nullptr;
   b->trial_helpers = getenv("TSIM_NO_TRIAL_HELPERS") ? 0 : 1;
+  b->pred_helpers = getenv("TSIM_NO_PREDICTOR_HELPERS") ? 0 : 1;
   b->ab_no_episode_lpt = getenv("TSIM_NO_EPISODE_LPT") != nullptr; b->ab_inkernel_readout = getenv("TSIM_INKERNEL_READOUT") != nullptr;
   b->ab_no_free_run = getenv("TSIM_NO_FREE_RUN") != nullptr; b->ab_lockstep = getenv("TSIM_LOCKSTEP") != nullptr; b->ab_no_default_opts = getenv("TSIM_NO_DEFAULT_OPTS") != nullptr;
   if (const char* e = getenv("TSIM_LPT_DEAL")) b->ab_lpt_deal = atoi(e);
@@ -1311,6 +1313,7 @@ int tsim_set_option(tsim_batch* b, int option, int value) {
   if (option == TSIM_OPT_VALUE_TRIALS) { if (value < 0) return fail("set_option: TSIM_OPT_VALUE_TRIALS >= 0"); b->value_trials = value; return 0; }
   if (option == TSIM_OPT_TRIAL_HELPERS) { b->trial_helpers = value != 0; return 0; }
   if (option == TSIM_OPT_VALUE_FIRST) { b->value_first = value != 0; return 0; }
+  if (option == TSIM_OPT_PREDICTOR_HELPERS) { b->pred_helpers = value != 0; return 0; }
   return fail("set_option: unknown option " + std::to_string(option));
 }
 int tsim_get_option(const tsim_batch* b, int option) {
@@ -1323,6 +1326,7 @@ int tsim_get_option(const tsim_batch* b, int option) {
   if (option == TSIM_OPT_ALL_DEFAULT) return default_options(b) ? 1 : 0;
   if (option == TSIM_OPT_FRAME_RECORDS) return b->last_frame_rec;
   if (option == TSIM_OPT_FORWARD_SPLIT) return b->last_fwd_split;
+  if (option == TSIM_OPT_PREDICTOR_HELPERS) return b->pred_helpers;
   return -1;
 }
 int tsim_set_solver_options(tsim_batch* b, int cross_kinks, int eval_budget) {

@@ -92,6 +92,29 @@ __device__ __forceinline__ void readout(const Ctx<R>& c, int lane, int env, bool
 // a helper slot (k_forward) must arrive at the same bits
 __device__ __forceinline__ float ts_trial_point(float base, float alpha, float dq) { return __builtin_fmaf(alpha, dq, base); }
 __device__ __forceinline__ double ts_trial_point(double base, double alpha, double dq) { return __builtin_fma(alpha, dq, base); }
+// force-free predictor of a BDF1 sub-step from the state before it, likewise ONE expression: the slot that starts the sub-step and a helper slot that
+// evaluates that predictor ahead of it (k_forward, predictor helpers)
+template <class R> __device__ __forceinline__ double ts_predictor_bdf1(double q0D, R h, R qd0) { return q0D + (double)h * (double)qd0; }
+// do k_forward's finished slots also evaluate a live slot's NEXT PREDICTOR (below: predictor helpers)?  The fused compiled-in BDF1 models, open loop,
+// several environments per wavefront.  (A BDF2 predictor needs the state two sub-steps back as well: left out.)  Every other instantiation — the
+// generic unit's above all — holds none of that code.
+template <class MS, class R, int NS, bool POLICY> constexpr bool ts_pred_helpers() {
+  if constexpr (POLICY || NS <= 1 || !ts_static_fused<MS, R>()) return false; else return MS::Iv(TSIM_IH_INTEGRATOR) != 2;
+}
+// a slot's share in the predictor jobs of one round; EMPTY where the instantiation has no predictor helpers, so that it holds nothing of them
+template <bool ON, class R> struct TsPredRound {
+  __device__ __forceinline__ bool trial(bool done) const { return done; }      // may this slot take a line-search trial?  (every finished slot)
+};
+template <class R> struct TsPredRound<true, R> {
+  bool th = false;      // this finished slot took no predictor job: it may take a line-search trial
+  int hp = -1;          // the slot that evaluated THIS slot's next predictor, or none
+  R gp = R(0);          // ... and the ||g|| it found there
+  __device__ __forceinline__ bool trial(bool) const { return th; }
+};
+__device__ __forceinline__ unsigned ts_drop_lowest(unsigned mask, int n, int nmax) {      // mask without its n (<= nmax) lowest set bits
+  for (int i = 0; i < nmax; ++i) { if (i < n) mask &= mask - 1u; }
+  return mask;
+}
 enum { TP_R_SIZE = 18, TP_D_SIZE = 12 };      // pose record of a (sensor, primitive) combination: R part, double part (k_readout)
 // the environments a read-out launch covers: order[e0 .. e0 + n) of a block -> environment map, or e0 .. e0 + n themselves (order null)
 struct TsSubRange { const int* order; int e0, n; };
@@ -123,6 +146,8 @@ template <class R> struct FwdArgs {
   int helpers = 0;             // slots that have finished their environment evaluate the NEXT line-search trials of a slot that is still in one (k_forward, main loop; TSIM_OPT_TRIAL_HELPERS)
   int frame_rec = 0;           // fused static instantiations: the frames' outputs (q, qd, variables, pose records) are written after the launch, from the tape, by
                                // k_frame_records (below); a slot that ends a frame only moves on to the next one (tsim_hip.hip launch_forward)
+  int pred_helpers = 0;        // finished slots evaluate the predictor of a live slot's NEXT sub-step in the round that may end its current one (k_forward, main loop;
+                               // TSIM_OPT_PREDICTOR_HELPERS; only where `helpers` holds).  Read in the loop's cold blocks only
 };
 
 // The outputs of the frame f that environment env has just finished — the final state in c.qD / c.qd (the link sweep) and c.q0D / c.qd0 (q, qd) —:
@@ -273,6 +298,37 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
   static_assert(NS <= 4, "helper slots: three result registers (gh0..gh2) and step factors 1/2, 1/4, 1/8 — at most three helpers per owner");
   if (helpers_on && !valid) { done = true; fs = false; ss = false; }      // an idle slot of the last wavefront helps from the start
   int helped = 0;
+  // Predictor helpers (round 28; ts_pred_helpers<>: the fused compiled-in BDF1 models; launches that record a tape and run free).  A typical sub-step
+  // is two rounds: the evaluation at the predictor (g, H: the Newton step) and the one at the trial point, which converges and is committed.  The NEXT
+  // sub-step's predictor is q1 + h qd1 of that trial point — known before the trial is evaluated.  So a `done` slot evaluates, in the round in which a
+  // live slot evaluates a point that may END its sub-step (the first evaluation of the sub-step, or the first trial of a full Newton step: ls <= 0), the
+  // predictor that follows IF that point is committed: q1 and qd1 by evaluate()'s own expressions (ts_point_qD / ts_point_qd), the predictor by
+  // the sub-step start's (ts_predictor_bdf1), the owner's control — its next frame's, `unext`, where the commit would end a frame —, its BDF1 coefficients and
+  // its parameter table.  The loop of these instantiations commits BEFORE it solves; a slot that has just committed and finds the predictor of exactly
+  // its new sub-step evaluated starts that sub-step at once, copies g, H and K from the helper's LDS, judges the point as the first evaluation of the
+  // sub-step and joins this round's solve: one round per sub-step instead of two, for as long as a finished co-slot exists.  If the adopted point
+  // itself ends the sub-step (a body at rest), the slot stays `fin` through the next round — which evaluates that very point again: c.q, c.qd of the
+  // commit; c.H and c.H2 are the adopted ones or the same bits again — and commits there.  A predictor whose owner did not commit is dropped.
+  // The evaluation is a function of its inputs only, so outputs, tape and `evals` are those of the loop without the option, bit for bit
+  // (tests/test_gpu_predictor_helpers.py); `helped` also counts the adopted predictors.  Such a round always computes tangents: in a launch that
+  // records a tape an owner at ls <= 0 is never value-only (`vo` is set by a halving, ls >= 1, or by `vfirst`, which needs a launch without tape), so
+  // the owner itself is one of the slots `tang` below asks for.  With several finished slots the first ones (in slot order) take the predictor jobs, one
+  // per owner, and the others the line-search trials as before: 100 of an environment's ~250 evaluations on TactilePush end a sub-step, far more than
+  // are rejected first trials (profiles/r28_predictor_helpers.md).
+  constexpr bool kPred = ts_pred_helpers<MS, R, NS, POLICY>();
+#define TS_NEWTON_STEPS \
+    if (__any(solve)) { \
+      solve_newton<R, NRM, LPE, double, ts_static_nr<MS>()>(c.H, c.rhs, c.dq, nr, false, lane, solve);      /* (elimination in fp32: -0.7 %, not taken; profiles/r04_static_model.md) */ \
+      if (solve) { \
+        alpha = R(1); ls = 0; \
+        vo = vfirst && kq * gn * gn < R(0.25) * c.tol;      /* the trial that will most likely end the sub-step: ||g|| only (see `vfirst` below) */ \
+        if (lane < nr) c.dl[lane] = dlbase[lane] + c.dq[lane]; \
+      } \
+      TS_SYNC(); \
+    }
+/* the evaluation this slot is about to make (or has just made: nothing in between changes it) may end its sub-step, and another sub-step follows it */
+#define pred_need (!done && !fin && !held && !wait_ && ls <= 0 && !forced && !(s == a.nsub - 1 && f == a.nframes - 1))
+#define pred_on (helpers_on && free_run && TS_RECORD != 0 && a.pred_helpers != 0)      /* (asked in the cold blocks only) */
   // Value-first trials (round 5; launches that record no tape).  A sub-step whose Newton iteration converges in ONE step — nearly all of them:
   // 2.07 evaluations per sub-step on TactileInsertion, 2.5 on D'Claw and TactilePush — is an evaluation at the predictor (g and H: the Newton step)
   // and one at the new point, of which only ||g|| < tol is used: H of the final iterate goes to the tape, and there is none.  So where the
@@ -290,10 +346,24 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
 #ifdef TS_ROUND_STATS   // A/B builds only (tools/round_stats.py): rounds of this wavefront and its shader clocks, left in status / gnorm
   int rounds_ = 0; const long long rs_t0_ = clock64();
   int fe_execs_ = 0; long long fe_cycles_ = 0;      // the frame-end block: times this wavefront ran it and the shader clocks it spent there, left in helped
+  // What a finished slot could do for a live one (tools/predictor_helper_sizing.py; TsFrameRecords<> launches leave these in helped instead, their frame-end
+  // block is empty), per slot: hr_ the rounds in which it was live while a slot of its wavefront was done at the start of the round; hc_ its commits in
+  // such rounds that another sub-step follows; hcs_ those of them whose evaluation was the first of the sub-step or a full Newton step's first trial
+  // (ls <= 0, not the step across a kink) while the done slots, dealt to the live ones in slot order, reached this one
+  int hr_ = 0, hc_ = 0, hcs_ = 0;
 #endif
   while (!__all(done)) {
 #ifdef TS_ROUND_STATS
     ++rounds_;
+    const bool hround_ = __any(done) && !done;
+    bool hserved_ = false;
+    const unsigned long long db_ = __ballot(done);      // (every lane takes part)
+    if (hround_) {
+      ++hr_;
+      int nd_ = 0, rk_ = 0;
+      for (int s_ = 0; s_ < NS; ++s_) { const int bit_ = (int)((db_ >> (s_ * LPE)) & 1ull); nd_ += bit_; if (s_ < slot) rk_ += 1 - bit_; }
+      hserved_ = rk_ < nd_;
+    }
 #endif
     if (POLICY ? __any(fs) : fs) {
       R uv = R(0);
@@ -342,7 +412,7 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
         }
       } else {
         c.cv = R(1) / c.h; c.ca = R(1) / (c.h * c.h);
-        if (lane < nr) { c.qpD[lane] = c.q0D[lane] + (double)c.h * (double)c.qd0[lane]; c.qp[lane] = (R)c.qpD[lane]; c.qdp[lane] = c.qd0[lane]; }
+        if (lane < nr) { c.qpD[lane] = ts_predictor_bdf1(c.q0D[lane], c.h, c.qd0[lane]); c.qp[lane] = (R)c.qpD[lane]; c.qdp[lane] = c.qd0[lane]; }
       }
       if (lane < nr) c.dl[lane] = R(0);          // initial guess: the predictor
       gn = R(0); alpha = R(1); iter = 0; ls = -1; sub_evals = 0; crossings = 0; conv = false; fin = false; forced = false; vo = false;
@@ -389,15 +459,43 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
     if (TS_UNLIKELY(helpers_on && __any(done))) {               // (cold code: laid out behind the loop's straight-line path)
       const bool need = !done && !fin && !held && !wait_ && ls >= 0 && !forced;      // in a line search: this round evaluates trial ls, the next would be ls + 1
       unsigned cm, nm; slot_masks(need, cm, nm);
+      TsPredRound<kPred, R> pr;
+      if constexpr (kPred) {
+        pr.th = done;
+        if (pred_on) {
+          unsigned cm_, pm; slot_masks(pred_need, cm_, pm);
+          const int npj = min(__popc(cm), __popc(pm));      // finished slots that take a predictor job this round: the first npj of them, in slot order
+          if (npj > 0) {                          // wave-uniform
+            const int j = __popc(cm & ((1u << slot) - 1u));
+            const bool job = done && j < npj;     // finished slot j evaluates the next predictor of the j-th such owner
+            const int owner = job ? nth(pm, j) : slot, src = owner * LPE + lane;
+            const int os = lane_gather(s, src);
+            const R oun = lane_gather(unext, src), oh = lane_gather(c.h, src), ocv = lane_gather(c.cv, src), oca = lane_gather(c.ca, src);
+            if (job) {
+              const int d = (owner - slot) * ts_lds_env_reals(c.nl, nr, nu, (int)sizeof(R));
+              if (lane < nr) {
+                // the owner's point of this round, as its evaluate() is about to form it, and what its commit and the start of its next sub-step would make of it
+                const R dlo = c.dl[lane + d], qd1 = ts_point_qd(c.qdp[lane + d], ocv, dlo);
+                const double qpn = ts_predictor_bdf1(ts_point_qD((c.qpD + d * (int)sizeof(R) / 8)[lane], dlo), oh, qd1);
+                c.qpD[lane] = qpn; c.qp[lane] = (R)qpn; c.qdp[lane] = qd1; c.dl[lane] = R(0);
+              }
+              if (lane < nu) c.u[lane] = os == a.nsub - 1 ? oun : c.u[lane + d];      // the commit would end the owner's frame: its next action, fetched a frame ahead
+              c.cv = ocv; c.ca = oca;             // (BDF1: the coefficients of every sub-step)
+              if (a.Fenv) c.F = lds + owner * (a.fstride + 2);
+            }
+            cm = ts_drop_lowest(cm, npj, NS - 1); pr.th = done && ((cm >> slot) & 1u) != 0;      // the other finished slots serve the line searches
+          }
+        }
+      }
       if (cm != 0 && nm != 0) {                   // wave-uniform
         const int m = __popc(nm);
         int owner = slot, off = 0;
-        if (done) { const int j = __popc(cm & ((1u << slot) - 1u)); owner = nth(nm, j % m); off = 1 + j / m; }      // helper j serves owner j mod m with its trial + 1 + j / m
+        if (pr.trial(done)) { const int j = __popc(cm & ((1u << slot) - 1u)); owner = nth(nm, j % m); off = 1 + j / m; }      // helper j serves owner j mod m with its trial + 1 + j / m
         // the owner's loop state (identical in all lanes of its slot) travels through the LDS crossbar; every lane takes part
         const int src = owner * LPE + lane;
         const int ols = lane_gather(ls, src);
         const R oalpha = lane_gather(alpha, src), ocv = lane_gather(c.cv, src), oca = lane_gather(c.ca, src);
-        if (done && ols + off <= c.max_ls) {
+        if (pr.trial(done) && ols + off <= c.max_ls) {
           const int d = (owner - slot) * ts_lds_env_reals(c.nl, nr, nu, (int)sizeof(R));   // this slot's LDS arrays -> the owner's
           const R ah = oalpha * (off == 1 ? R(0.5) : off == 2 ? R(0.25) : R(0.125));
           if (lane < nr) {
@@ -418,10 +516,22 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
     //      ||g|| they found — scalars, not arrays: a dynamically indexed array would live in scratch memory
     int nh = 0, hs0 = slot, hs1 = slot, hs2 = slot;
     R gh0 = gnew, gh1 = gnew, gh2 = gnew;
+    TsPredRound<kPred, R> po;                  // (predictor helpers) who evaluated this slot's next predictor this round
     if (TS_UNLIKELY(helpers_on && __any(done))) {
       if (a.Fenv) c.F = lds + slot * (a.fstride + 2);
       const bool need = !done && !fin && !held && !wait_ && ls >= 0 && !forced;      // (the state the helpers were assigned from: nothing has changed it)
       unsigned cm, nm; slot_masks(need, cm, nm);
+      if constexpr (kPred) {
+        if (pred_on) {
+          const bool pn = pred_need;
+          unsigned cm_, pm; slot_masks(pn, cm_, pm);
+          const int npj = min(__popc(cm), __popc(pm)), rp = __popc(pm & ((1u << slot) - 1u));
+          if (pn && rp < npj && tang) po.hp = nth(cm, rp);      // (a helper's evaluation without tangents left no H and K to take over: never adopted.  Today such a round
+                                                                // always computes them — see `kPred` above —; this keeps a later change to `vo` from adopting a stale matrix)
+          po.gp = lane_gather(gnew, (po.hp >= 0 ? po.hp : slot) * LPE + lane);
+          cm = ts_drop_lowest(cm, npj, NS - 1);
+        }
+      }
       if (cm != 0 && nm != 0) {
         const int m = __popc(nm), kc = __popc(cm), r_ = __popc(nm & ((1u << slot) - 1u));
         if (need) nh = r_ < kc ? (kc - r_ + m - 1) / m : 0;
@@ -473,6 +583,9 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
       if (lane < nr) c.dl[lane] = ts_trial_point(dlbase[lane], alpha, c.dq[lane]);
       return true;
     };
+#ifdef TS_ROUND_STATS
+    if (ls > 0 || forced) hserved_ = false;      // (before the judgement: the evaluation this round made)
+#endif
     if (!fin && !done && !wait_) {
       bool halved = judge(gnew, 0, slot);      // this slot's own evaluation (the one straight-line call of every round) ...
       if (TS_UNLIKELY(nh > 0)) {               // ... then its helpers', in the order the sequential loop would have made those evaluations
@@ -499,15 +612,10 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
       }
     }
     TS_SYNC();
-    if (__any(solve)) {
-      solve_newton<R, NRM, LPE, double, ts_static_nr<MS>()>(c.H, c.rhs, c.dq, nr, false, lane, solve);      // (elimination in fp32: -0.7 %, not taken; profiles/r04_static_model.md)
-      if (solve) {
-        alpha = R(1); ls = 0;
-        vo = vfirst && kq * gn * gn < R(0.25) * c.tol;      // the trial that will most likely end the sub-step: ||g|| only (see `vfirst` above)
-        if (lane < nr) c.dl[lane] = dlbase[lane] + c.dq[lane];
-      }
-      TS_SYNC();
-    }
+    // the Newton steps of the slots that took a point which does not end their sub-step.  ONE piece of text (TS_NEWTON_STEPS, defined in front of the
+    // loop); the predictor-helper instantiations run it behind the commit block, the others in front of it as ever (commit acts on `fin` slots, this on
+    // `solve` slots — disjoint — and the solve only reads c.H)
+    if constexpr (!kPred) { TS_NEWTON_STEPS }
     // ---- commit the sub-steps that ended with this evaluation: c.q = q1, c.qd = (q1 - q0)/h, c.H = dg/dq1 at q1
     bool commit = fin && !done && !held;
     if (TS_OPT(lockstep, 0) && !__all(fin || done)) commit = false;      // the slots of a wavefront go through the sub-steps together (see FwdArgs)
@@ -517,6 +625,9 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
     }
     bool frame_end = false;
     if (commit) {
+#ifdef TS_ROUND_STATS
+      if (hround_ && !(s == a.nsub - 1 && f == a.nframes - 1)) { ++hc_; if (hserved_) ++hcs_; }
+#endif
       if (!conv) ++bad;
       gmax = t_max(gmax, gn);
       if (TS_RECORD && valid) {
@@ -524,8 +635,10 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
         if (lane < nr) { rec_q(rec)[lane] = c.qD[lane]; rec[rec_qd<R>(nr) + lane] = c.qd[lane]; }
         for (int e = lane; e < nr * nr; e += LPE) rec[rec_H<R>(nr) + e] = c.H[e];
         if (lane < nu) rec[rec_u<R>(nr) + lane] = c.u[lane];
-        // K of the same evaluation as H (evaluate_static_fused: c.H2).  A commit always follows this slot's OWN evaluation with tangents of
-        // the committed point while recording (judge: a helper's result is adopted only when a Newton step follows), so c.H and c.H2 match
+        // K of the same evaluation as H (evaluate_static_fused: c.H2).  While recording, a commit follows this slot's OWN evaluation with tangents of
+        // the committed point (judge: a trial helper's result is adopted only when a Newton step follows), so c.H and c.H2 match — or, with predictor
+        // helpers, an adopted predictor that ended its sub-step at once: then c.H and c.H2 are BOTH the helper's, copied together at the adoption, and
+        // the round in between either computed no tangents (they are the copies) or computed the same point's again (the same bits)
         if constexpr (ts_static_fused<MS, R>()) { if (a.tk) for (int e = lane; e < nr * nr; e += LPE) rec[rec_K<R>(nr, nu) + e] = c.H2[e]; }
       }
       TS_SYNC();
@@ -538,6 +651,34 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
       if (++s == a.nsub) { s = 0; frame_end = true; }
     }
     TS_SYNC();
+    if constexpr (kPred) {
+      // ---- (predictor helpers) a slot that has just committed and whose new sub-step's predictor was evaluated by slot hp this round — the helper set
+      //      out from the very point that was committed: a commit follows this slot's own evaluation — starts the sub-step here and takes that evaluation
+      //      as its first: g, H and K from the helper's LDS, judged as `judge` judges a first evaluation (always taken: the round computed tangents)
+      if (TS_UNLIKELY(__any(po.hp >= 0 && commit))) {
+        if (po.hp >= 0 && commit) {
+          // the start of the sub-step (above; BDF1, and `waited` is vfirst's, which needs a launch without tape) ...
+          c.cv = R(1) / c.h; c.ca = R(1) / (c.h * c.h);
+          if (lane < nr) { c.qpD[lane] = ts_predictor_bdf1(c.q0D[lane], c.h, c.qd0[lane]); c.qp[lane] = (R)c.qpD[lane]; c.qdp[lane] = c.qd0[lane]; c.dl[lane] = R(0); }
+          alpha = R(1); iter = 0; ls = -1; crossings = 0; conv = false; forced = false; vo = false; ss = false;
+          // ... its first evaluation, the helper's ...
+          const int d = (po.hp - slot) * ts_lds_env_reals(c.nl, nr, nu, (int)sizeof(R));
+          if (lane < nr) c.g[lane] = c.g[lane + d];
+          for (int e = lane; e < nr * nr; e += LPE) { c.H[e] = c.H[e + d]; c.H2[e] = c.H2[e + d]; }
+          ++evals; sub_evals = 1; ++helped;
+          // ... and what a taken point means at ls < 0 (above): the sub-step ends there, or a Newton step follows
+          gn = po.gp; fin = true;
+          if (!ts_finite(gn)) nonfinite = true;
+          else if (gn < c.tol) conv = true;
+          else if (!(iter >= c.max_iter || (TS_OPT(eval_budget, 0) > 0 && sub_evals >= TS_OPT(eval_budget, 0)))) {
+            fin = false; solve = true;
+            if (lane < nr) { c.rhs[lane] = -c.g[lane]; dlbase[lane] = c.dl[lane]; }
+          }
+        }
+        TS_SYNC();
+      }
+      TS_NEWTON_STEPS
+    }
     // ---- end of a frame (per slot in a free-running launch, all slots together otherwise): the link poses / velocities in LDS are
     //      those of the accepted state (last evaluation)
     if constexpr (kFrameRec) {
@@ -593,10 +734,14 @@ __device__ __forceinline__ void ts_forward(const FwdArgs<R>& a) {
 #ifdef TS_ROUND_STATS
     if (lane == 0) { if (a.gnorm) a.gnorm[env] = (float)(clock64() - rs_t0_); if (a.status) a.status[env] = rounds_; }
     if (lane == 0 && a.helped) a.helped[env] = (int)(fe_cycles_ < (1ll << 23) - 1 ? fe_cycles_ : (1ll << 23) - 1) * 256 + (fe_execs_ < 255 ? fe_execs_ : 255);
+    if (kFrameRec && lane == 0 && a.helped) a.helped[env] = min(hr_, 2047) | min(hc_, 1023) << 11 | min(hcs_, 1023) << 21;
 #endif
   }
 }
 #undef helpers_on
+#undef pred_on
+#undef pred_need
+#undef TS_NEWTON_STEPS
 #undef TS_OPT
 #undef TS_RECORD
 template <class R, int NRM, bool EXPJ, int LPE, bool POLICY = false, class MS = void>

@@ -12,9 +12,14 @@ batched over the environments in torch, in information form.  A pair's parameter
 SENSOR's own parameters have one), so what the pad feels of them is the box's and the pad's changed motion, C_f E_f.  Prints the relative
 parameter error at the end with the tactile update and without it (prediction alone, which stays at the prior: the nominal values).
 
-    python examples/push_tactile_param_ekf.py [--envs 64] [--frames 20] [--sigma 0.1]
+    python examples/push_tactile_param_ekf.py [--envs 64] [--frames 20] [--sigma 0.1] [--normal-equations]
 
-It is a demonstration, not a test: there is no threshold.  What it printed on an MI355X is in profiles/r26_param_jacobians.md."""
+With --normal-equations the update's H_f^T H_f and H_f^T y_f come from ONE launch (include/tsim.h tsim_tactile_normal_equations,
+functions.episode_information) and neither C_f nor F_f is stored; the replays then run on a second batch, because the launch reads the recorded
+tape with the measurements as its residual.  Without the flag nothing changes.
+
+It is a demonstration, not a test: there is no threshold.  What it printed on an MI355X is in profiles/r26_param_jacobians.md, and with the flag
+next to it in profiles/r29_tactile_normal_equations.md."""
 import argparse
 import os
 import sys
@@ -23,7 +28,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tactilesimulation_amd.functions import episode_observation, episode_parameters, episode_transition      # noqa: E402
+from tactilesimulation_amd.functions import episode_information, episode_observation, episode_parameters, episode_transition      # noqa: E402
 from tactilesimulation_amd.host.batch import BatchSim      # noqa: E402
 from tactilesimulation_amd.model.compiler import load_model      # noqa: E402
 from tactilesimulation_amd.workloads import asset, push_workload      # noqa: E402
@@ -31,7 +36,7 @@ from tactilesimulation_amd.workloads import asset, push_workload      # noqa: E4
 PARAMS = (("tactile_pad_left", "box"), ("kn", "mu"))      # the pad-box pair's normal stiffness and friction coefficient
 
 
-def run(nenv=64, T=20, S=5, sigma=0.1, seed=0, device="cuda:0", verbose=True):
+def run(nenv=64, T=20, S=5, sigma=0.1, seed=0, device="cuda:0", verbose=True, normal_equations=False):
     dt = torch.float64
     m = load_model(asset("pusher"))
     cols = [m.table_offset("pair", PARAMS[0], f) for f in PARAMS[1]]
@@ -52,27 +57,36 @@ def run(nenv=64, T=20, S=5, sigma=0.1, seed=0, device="cuda:0", verbose=True):
     xref = torch.cat([ref["q"], ref["qd"]], 2)                                # [T, nenv, nx]: x_{f+1}
     # 2. the linearisation, one launch each; the parameter columns scaled to relative changes
     A, _ = episode_transition(sim, T, S)
-    C = episode_observation(sim, T, S)                                        # [T, nenv, ntac, nx]
-    E, F = episode_parameters(sim, T, S, cols)                                # [T, nenv, nx, np], [T, nenv, ntac, np]
-    E, F = E * pnom, F * pnom
-    assert not bool(F.any())                                                  # a pair column has no direct tactile term
+    if normal_equations:                                                      # E alone: no Ct, no F
+        E = sim.param_jacobians(T, S, cols, want_E=True)["E"] * pnom
+        C = F = H = Ht = None
+    else:
+        C = episode_observation(sim, T, S)                                    # [T, nenv, ntac, nx]
+        E, F = episode_parameters(sim, T, S, cols)                            # [T, nenv, nx, np], [T, nenv, ntac, np]
+        E, F = E * pnom, F * pnom
+        assert not bool(F.any())                                              # a pair column has no direct tactile term
+        H = torch.cat([C, F], 3)                                              # [T, nenv, ntac, nz]
+        Ht = H.transpose(-1, -2).contiguous()
     Az = torch.zeros((T, nenv, nz, nz), device=device, dtype=dt)
     Az[:, :, :nx, :nx], Az[:, :, :nx, nx:] = A, E
     Az[:, :, nx:, nx:] = torch.eye(np_, device=device, dtype=dt)
-    H = torch.cat([C, F], 3)                                                  # [T, nenv, ntac, nz]
-    Ht = H.transpose(-1, -2).contiguous()
     # 3. replays with the parameters perturbed per environment; their tactile frames are the measurements
     rng = np.random.default_rng(seed + 2)
     dp_true = torch.tensor(sigma * rng.uniform(-1, 1, size=(nenv, np_)), device=device, dtype=dt)      # relative
     tab = base.clone()
     tab[:, cols] = pnom * (1 + dp_true)
-    sim.set_env_tables(tab)
-    sim.reset(q0, None, backward_flag=False)
-    rep = sim.rollout(ut, S, want_qd=True)
+    rsim = BatchSim(m, nenv, device=device, dtype=dt, tape_capacity=T * S) if normal_equations else sim      # (sim keeps the recorded tape)
+    rsim.set_env_tables(tab)
+    rsim.reset(q0, None, backward_flag=False)
+    rep = rsim.rollout(ut, S, want_qd=True)
     dx_true = torch.cat([rep["q"], rep["qd"]], 2) - xref
     y = rep["tactile"] - ref["tactile"]                                       # [T, nenv, ntac]
     loaded = ref["tactile"].abs() > 0
     r = 0.05 * float(ref["tactile"][loaded].pow(2).mean().sqrt()) if bool(loaded.any()) else 1.0      # 5 % of a loaded taxel's typical force
+    if normal_equations:                                                      # H^T H and H^T y of every frame in one launch (W = I; 1 / r^2 below)
+        scale = torch.cat([torch.ones(nx, device=device, dtype=dt), pnom])
+        HtH, Hty = episode_information(sim, T, S, residual=y.contiguous(), cols=cols)
+        HtH, Hty = HtH * scale[:, None] * scale[None, :], Hty * scale
     # 4. the filter, with and without the tactile update
     p0 = torch.full((nz,), 1e-12, device=device, dtype=dt)                    # the start state is known
     p0[nx:] = sigma ** 2
@@ -89,8 +103,8 @@ def run(nenv=64, T=20, S=5, sigma=0.1, seed=0, device="cuda:0", verbose=True):
             P = Az[f] @ P @ Az[f].transpose(1, 2) + Q
             if update:
                 Pinv = torch.linalg.solve(P, eye.expand(nenv, -1, -1))
-                info = Pinv + (Ht[f] @ H[f]) / r ** 2                         # H^T R^-1 H: nz x nz
-                eta = Pinv @ z + (Ht[f] @ y[f].unsqueeze(2)) / r ** 2
+                info = Pinv + (HtH[f] if normal_equations else Ht[f] @ H[f]) / r ** 2      # H^T R^-1 H: nz x nz
+                eta = Pinv @ z + (Hty[f].unsqueeze(2) if normal_equations else Ht[f] @ y[f].unsqueeze(2)) / r ** 2
                 P = torch.linalg.solve(info, eye.expand(nenv, -1, -1))
                 P = 0.5 * (P + P.transpose(1, 2))
                 z = P @ eta
@@ -105,7 +119,10 @@ def run(nenv=64, T=20, S=5, sigma=0.1, seed=0, device="cuda:0", verbose=True):
         pr = lambda a: "median %.3e  max %.3e" % (np.median(a), a.max())      # noqa: E731
         print("TactilePush fp64, %d environments, %d frames of %d sub-steps; pad-box %s perturbed by up to %g of their values (%s)" % (
             nenv, T, S, " and ".join(PARAMS[1]), sigma, ", ".join("%g" % v for v in pnom.tolist())))
-        print("E %s, F %s (zero: pair columns), C %s; measurement sigma %.3e" % (tuple(E.shape), tuple(F.shape), tuple(C.shape), r))
+        if normal_equations:
+            print("E %s, H^T H %s, H^T y %s from one launch (no C, no F); measurement sigma %.3e" % (tuple(E.shape), tuple(HtH.shape), tuple(Hty.shape), r))
+        else:
+            print("E %s, F %s (zero: pair columns), C %s; measurement sigma %.3e" % (tuple(E.shape), tuple(F.shape), tuple(C.shape), r))
         for k, name in enumerate(PARAMS[1]):
             print("relative error of %-3s  at the prior (prediction alone) : %s" % (name, pr(res["prediction"][-1][:, k])))
             print("relative error of %-3s  with the tactile update         : %s" % (name, pr(res["tactile"][-1][:, k])))
@@ -122,5 +139,6 @@ if __name__ == "__main__":
     ap.add_argument("--envs", type=int, default=64)
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--sigma", type=float, default=0.1)
+    ap.add_argument("--normal-equations", action="store_true", help="H^T H and H^T y from tsim_tactile_normal_equations; no C or F is stored")
     a = ap.parse_args()
-    run(nenv=a.envs, T=a.frames, sigma=a.sigma)
+    run(nenv=a.envs, T=a.frames, sigma=a.sigma, normal_equations=a.normal_equations)

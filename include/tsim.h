@@ -267,8 +267,9 @@ int tsim_frame_jacobians_launch_info(const tsim_batch* b, int32_t* out);
  * num_frames or num_steps < 1; a model without taxels; a model whose block would not fit the 64 KB of LDS; more than 2^31 - 1 blocks.  The mask is
  * device memory, which this call does not read on the host: with no masked frame every block returns at once and nothing is written (the Python
  * layer, which builds the mask, refuses such a call).
- * Out of scope: geometry as inputs; the fused closed-loop tape; the B = 1 shim; products such as C^T W C.  (The contact-group table columns as
- * inputs, F_f = dtactile / dp, have their own entry: tsim_param_jacobians below.) */
+ * Out of scope: geometry as inputs; the fused closed-loop tape; the B = 1 shim.  (The contact-group table columns as inputs, F_f = dtactile / dp,
+ * have their own entry: tsim_param_jacobians below; so have the products H^T W H and H^T W r of H = [C_f | F_f], which never store C_f:
+ * tsim_tactile_normal_equations.) */
 int tsim_tactile_jacobians(tsim_batch* b, int num_frames, int num_steps, const int32_t* tactile_slot, void* Ct_out, void* stream);
 /* Diagnostics: the static launch geometry of a tsim_tactile_jacobians call, as tsim_frame_jacobians_launch_info reports: out[0] = LDS bytes per
  * block (the contexts and the slots' record blocks), out[1] = threads per block, out[2] = blocks PER FRAME, out[3] = lanes per environment: the
@@ -313,6 +314,43 @@ int tsim_param_jacobians(tsim_batch* b, int num_frames, int num_steps, int ncols
  * PER FRAME, out[3] = lanes per environment: the batch's, doubled until a block fits 64 KB; they depend neither on ncols nor on which outputs are
  * asked for.  out = int32[4]. */
 int tsim_param_jacobians_launch_info(const tsim_batch* b, int32_t* out);
+
+/* Tactile normal equations (no reference counterpart): the information form of the tactile block of a taped episode's linearisation,
+ *     N_f = H_f^T W H_f ,      n_f = H_f^T W r_f ,      H_f = [C_f | F_f]   (ndof_tactile x Z),   Z = 2 ndof_r + (with_params ? 4 nsensor : 0),
+ * for every masked frame of the newest num_frames * num_steps taped sub-steps in ONE launch, without C_f or F_f ever being stored: what an
+ * information filter (info = P^-1 + H^T R^-1 H, eta = P^-1 z + H^T R^-1 y) and Gauss-Newton / LM on tactile residuals consume.  C_f is exactly
+ * tsim_tactile_jacobians' C_f (x = (q, qdot) at the frame's END state); F_f is the dense form of tsim_param_jacobians' compact Ft: column
+ * 2 ndof_r + 4 s + k is field k (kn, kt, mu, damping) of sensor s, non-zero only on that sensor's taxels.  The window and tactile_slot are
+ * tsim_tactile_jacobians' (a DEVICE int32 mask; NULL: slot f).
+ *   weight  DEVICE [ndof_tactile] or NULL (ones): the diagonal of W, an inverse variance per tactile value, shared by all environments and
+ *           frames.  It is not read on the host: negative or non-finite weights are the caller's business (they enter the sums as they are, on
+ *           the loaded taxels only).
+ *   resid   DEVICE [num_masked][B][ndof_tactile] or NULL: r.
+ *   N_out   [num_masked][B][Z][Z], dense, row-major, EXACTLY symmetric (an entry is computed once and mirrored).  Not NULL.
+ *   n_out   [num_masked][B][Z]; given if and only if resid is.
+ * Device memory, the batch's real type.  Z^2 + Z reals per environment and masked frame: TactilePush with parameters, fp32: 1 368 bytes, where
+ * Ct and Ft together are 27 300.  r^T W r is not computed (it needs the unloaded taxels too).
+ * A taxel's rows are summed over its sensor's primitives BEFORE the product.  The sums run over the loaded taxels in ascending order, one fixed
+ * order at every launch shape, without atomics: a frame's bits depend neither on num_frames, nor on the mask, nor on the batch size or the
+ * environment's position in the batch; the state block N[:2 ndof_r, :2 ndof_r] and n[:2 ndof_r] have the same bits with and without with_params,
+ * and N with and without resid.  Exact zeros: a frame in which no taxel is loaded gives all-zero N and n; a sensor without primitives or
+ * without a loaded taxel exactly zero parameter rows and columns; the blocks between two sensors' parameter columns are exactly zero.  Every
+ * entry of both outputs is written on every call.  Parameters are the environment's row of tsim_set_env_tables, or the shared model's.  BDF2 and
+ * rotation-vector models are accepted: only the (q, qdot) of the frame's last tape record is read, nothing is solved.
+ * Read-only: the tape is not popped; the state, the carried adjoint, the cache and the pose records are untouched.  No device copy, no
+ * allocation, no host synchronisation; capturable.  A compiled-in model's batch runs the generic evaluation on its tape.
+ * Returns non-zero (tsim_last_error) and launches nothing for: a null batch or a null N_out; exactly one of resid and n_out given; no tape
+ * recorded or a window longer than the tape; num_frames or num_steps < 1; a model without taxels; a model whose block would not fit the 64 KB of
+ * LDS; more than 2^31 - 1 blocks.  With no masked frame in the device mask every block returns at once and nothing is written.
+ * Out of scope: a full (non-diagonal) W; r^T W r; the pair and dof-damping columns (no direct tactile term: exact zeros, which
+ * functions.episode_information fills in); the fused closed-loop tape; the B = 1 shim. */
+int tsim_tactile_normal_equations(tsim_batch* b, int num_frames, int num_steps, const int32_t* tactile_slot, int with_params,
+                                  const void* weight, const void* resid, void* N_out, void* n_out, void* stream);
+/* Diagnostics: the static launch geometry of a tsim_tactile_normal_equations call, as tsim_frame_jacobians_launch_info reports: out[0] = LDS
+ * bytes per block (the contexts, the slots' records, sums and row tiles, the entry table), out[1] = threads per block, out[2] = blocks PER
+ * FRAME, out[3] = lanes per environment: the batch's, doubled until a block fits 64 KB (at 64 lanes the taxels per trip halve instead).  They
+ * depend on with_params and on nothing else of a call.  out = int32[4]. */
+int tsim_tactile_normal_equations_launch_info(const tsim_batch* b, int with_params, int32_t* out);
 
 /* sim.backward() results df_dq0 / df_dqdot0                    envs/redmax_torch_functions.py:92-100
  * = the carried adjoint once the whole tape has been popped. [B][ndof_r] each. */

@@ -709,7 +709,7 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   p.kernel = kernel; p.policy = policy; p.lpe = L.lpe; p.grid = L.grid; p.lds = L.lds;
   p.expj = b->has_exp; p.nrm = b->has_exp || b->nr > 8 ? 16 : 8;      // rows of the register solve (a rotation-vector joint: 16, at 64 lanes: launch_shape)
   const bool adjoint = kernel == TS_K_BACKWARD || kernel == TS_K_BACKWARD_Z || kernel == TS_K_CLOSED_BACKWARD_Z;
-  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || kernel == TS_K_FRAME_JACOBIAN || kernel == TS_K_TACTILE_JACOBIAN || kernel == TS_K_PARAM_JACOBIAN || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
+  p.variant = kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_CLOSED_TANGENT || kernel == TS_K_FRAME_JACOBIAN || kernel == TS_K_TACTILE_JACOBIAN || kernel == TS_K_PARAM_JACOBIAN || kernel == TS_K_TACTILE_NORMAL || (adjoint && !b->tape_k_ok) ? TS_KM_GENERIC : kernel_mode(b, forced);
   if (p.variant != TS_KM_GENERIC && !pusher_instantiated(b, kernel, policy, false, p.lpe)) p.variant = TS_KM_GENERIC;
   p.default_opts = p.variant != TS_KM_GENERIC && default_options(b) && pusher_instantiated(b, kernel, policy, true, p.lpe);
   p.fused = p.variant == TS_KM_STATIC ? ts_static_fused<TsStaticPusher, float>() : p.variant == TS_KM_PARAM && ts_static_fused<TsParamPusher, float>();
@@ -728,6 +728,8 @@ static TsPlan ts_plan(const tsim_batch* b, int kernel, bool policy, int lpe) {
   if (kernel == TS_K_TACTILE_JACOBIAN) return slot_block_plan(b, p, ts_tj_slot_reals(b->nr), 0).plan;
   // the parameter Jacobians likewise: every slot holds TS_PJ_MAX_COLS columns behind the contexts (tsim_param_jacobian.h), whatever the launch selects
   if (kernel == TS_K_PARAM_JACOBIAN) return slot_block_plan(b, p, ts_pj_slot_reals(b->nr), 0).plan;
+  // (the tactile normal equations, TS_K_TACTILE_NORMAL: the batch's shape here; their block depends on the call's with_params and on the taxels per
+  // trip, so tactile_normal_plan widens the lanes and sizes the block)
   return p;
 }
 // the kernel arguments that come from the batch; each launch sets its own
@@ -1116,6 +1118,41 @@ static int launch_tactile_jacobians(tsim_batch* b, int T, int S, const int32_t* 
   return 0;
 }
 
+// The tactile normal equations of the masked frames of the newest T x S taped sub-steps (tsim_tactile_normal_equations): one launch of the generic
+// k_tactile_normal, T x ceil(B / NS) blocks (a block of a frame that is not masked returns at once), whatever the batch's view, on the batch's
+// per-environment rows.  Reads the tape, writes the caller's buffers.  The plan: the batch's shape; the lanes double while the contexts, the slots'
+// blocks (tsim_tactile_normal.h, a tile row per lane) and the entry table are over the cap; at 64 lanes the taxels per trip halve instead, down
+// to TS_TN_MIN_ROWS.  It depends on with_params and on nothing else of the call
+struct TnPlan { TsPlan plan; size_t ctx_lds, toff; int rows; };
+static TnPlan tactile_normal_plan(const tsim_batch* b, int with_params) {
+  TsPlan p = ts_plan(b, TS_K_TACTILE_NORMAL, false, 0);
+  const int wp = with_params ? 1 : 0;
+  auto blocks = [&](int lpe, int rows) { return (((size_t)(TS_WAVE / lpe) * ts_tn_slot_reals(b->nr, wp, rows) * b->esz + 15) / 16) * 16; };
+  auto bytes = [&](int lpe, int rows) { return lds_bytes_for(b, TS_WAVE / lpe) + blocks(lpe, rows) + (size_t)ts_tn_table_bytes(b->nr, wp); };
+  while (p.lpe < TS_WAVE && bytes(p.lpe, p.lpe) > TS_TAN_LDS_CAP) p.lpe *= 2;
+  int rows = p.lpe;
+  while (rows > TS_TN_MIN_ROWS && bytes(p.lpe, rows) > TS_TAN_LDS_CAP) rows /= 2;
+  const int ns = TS_WAVE / p.lpe;
+  p.grid = (unsigned)((b->B + ns - 1) / ns);
+  const size_t ctx_lds = lds_bytes_for(b, ns);
+  p.lds = bytes(p.lpe, rows);
+  return {p, ctx_lds, ctx_lds + blocks(p.lpe, rows), rows};
+}
+template <class R>
+static int launch_tactile_normal(tsim_batch* b, int T, int S, const int32_t* tac_slot, int with_params, const void* weight, const void* resid, void* N_out, void* n_out, hipStream_t st) {
+  auto [plan, ctx_lds, toff, rows] = tactile_normal_plan(b, with_params);
+  if (plan.lds > TS_TAN_LDS_CAP) return fail("tactile_normal_equations: a pair's per-dof records, the sums and a tile of " + std::to_string((int)TS_TN_MIN_ROWS) + " taxels do not fit the block's LDS next to the context for this model");
+  if ((unsigned long long)plan.grid * (unsigned)T > 0x7fffffffull) return fail("tactile_normal_equations: too many blocks");
+  TnArgs<R> a{};
+  pg_common<R>(b, a, T * S, T, S);      // a chunk is a frame
+  a.cull = b->pair_cull; a.xoff = (int)(ctx_lds / b->esz); a.toff = (int)toff; a.rows = rows; a.with_params = with_params ? 1 : 0;
+  a.tac_slot = tac_slot; a.weight = (const R*)weight; a.resid = (const R*)resid; a.N_out = (R*)N_out; a.n_out = (R*)n_out;
+  plan.grid *= (unsigned)T;
+  if (!TsLaunch<void, false, R>::run(plan, st, a)) return fail("no k_tactile_normal instantiation for the launch plan");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // The per-frame parameter Jacobians over the newest T x S taped sub-steps (tsim_param_jacobians): one launch of the generic k_param_jacobian,
 // T x ceil(B / NS) blocks, whatever the batch's view, on the batch's per-environment rows.  Reads the tape, writes the caller's buffers.  The
 // plan: as frame_jacobian_plan, the slot's block sized for TS_PJ_MAX_COLS columns whatever the launch selects
@@ -1274,6 +1311,10 @@ int tsim_tactile_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
 int tsim_param_jacobians_launch_info(const tsim_batch* b, int32_t* out) {
   if (!b || !out) return fail("param_jacobians_launch_info: null argument");
   return plan_info(param_jacobian_plan(b).plan, out);
+}
+int tsim_tactile_normal_equations_launch_info(const tsim_batch* b, int with_params, int32_t* out) {
+  if (!b || !out) return fail("tactile_normal_equations_launch_info: null argument");
+  return plan_info(tactile_normal_plan(b, with_params).plan, out);
 }
 int tsim_kernel_timing(tsim_batch* b, int enable) { b->kt_on = enable ? 1 : 0; return 0; }
 int tsim_kernel_times(tsim_batch* b, double* ms_sum, int32_t* launches) {
@@ -1593,6 +1634,19 @@ int tsim_tactile_jacobians(tsim_batch* b, int num_frames, int num_steps, const i
   if (int rc = taped_window(b, "tactile_jacobians", num_frames, num_steps, &n)) return rc;
   TS_DEVICE(b);
   return by_real(b, [&](auto r) { return launch_tactile_jacobians<decltype(r)>(b, num_frames, num_steps, tactile_slot, Ct_out, (hipStream_t)stream); });
+}
+
+int tsim_tactile_normal_equations(tsim_batch* b, int num_frames, int num_steps, const int32_t* tactile_slot, int with_params, const void* weight, const void* resid,
+                                  void* N_out, void* n_out, void* stream) {
+  if (!b) return fail("tactile_normal_equations: null batch");
+  if (b->ntax <= 0) return fail("tactile_normal_equations: the model has no taxels");
+  if (!N_out) return fail("tactile_normal_equations: null N_out");
+  if ((resid != nullptr) != (n_out != nullptr)) return fail("tactile_normal_equations: resid and n_out go together (one of them is null)");
+  if (!b->record || b->t_cur <= 0) return fail("tactile_normal_equations: no tape recorded (reset(backward_flag=True), then a roll-out)");
+  long long n;
+  if (int rc = taped_window(b, "tactile_normal_equations", num_frames, num_steps, &n)) return rc;
+  TS_DEVICE(b);
+  return by_real(b, [&](auto r) { return launch_tactile_normal<decltype(r)>(b, num_frames, num_steps, tactile_slot, with_params, weight, resid, N_out, n_out, (hipStream_t)stream); });
 }
 
 // table column -> compact index in ts_pg_count order ([pair kn kt mu kd], [sensor kn kt mu kd], [dof damping]: launch_param_grad's segments), or -1

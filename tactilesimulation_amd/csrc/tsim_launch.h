@@ -1,7 +1,7 @@
 // tsim_launch.h — launch plans of the simulation kernels and the one launcher that runs them.
 //
 // A plan (TsPlan, made by tsim_hip.hip ts_plan and nowhere else) names one instantiation of k_forward, k_backward, k_backward_z, k_closed_backward_z, k_debug_eval,
-// k_frame_records, k_param_grad, k_param_grad_body, k_tangent, k_tangent_body_src, k_closed_tangent, k_frame_jacobian, k_tactile_jacobian or k_param_jacobian and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
+// k_frame_records, k_param_grad, k_param_grad_body, k_tangent, k_tangent_body_src, k_closed_tangent, k_frame_jacobian, k_tactile_jacobian, k_param_jacobian or k_tactile_normal and the shape of its launch.  TsLaunch<MS, POLICY, R>::run launches it, for every view alike: MS = void, the generic kernels
 // (tsim_hip.hip; the parameter passes: tsim_param_grad.hip, tsim_param_grad_body.hip; the tangent pass: tsim_tangent.hip, tsim_tangent_body.hip, tsim_tangent_closed.hip), or a compiled-in model (tsim_static.h), whose translation units hold nothing but the
 // explicit instantiations of TsLaunch for their view: they are built with flags of their own (host/buildhash.py HIP_UNITS).
 #pragma once
@@ -13,6 +13,7 @@
 #include "tsim_frame_jacobian.h"
 #include "tsim_tactile_jacobian.h"
 #include "tsim_param_jacobian.h"
+#include "tsim_tactile_normal.h"
 #include "tsim_static_pusher.h"
 
 enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, TS_K_PARAM_GRAD, TS_K_PARAM_GRAD_BODY, TS_K_FRAME_RECORDS,
@@ -22,7 +23,8 @@ enum TsKernel { TS_K_FORWARD, TS_K_BACKWARD, TS_K_BACKWARD_Z, TS_K_DEBUG_EVAL, T
                 TS_K_CLOSED_TANGENT,           // the tangent pass through the fused closed loop (k_closed_tangent, tsim_tangent_closed.hip): generic view only, TactilePush (NRM 8)
                 TS_K_FRAME_JACOBIAN,           // the per-frame transition Jacobians (k_frame_jacobian, tsim_frame_jacobian.hip): generic view only
                 TS_K_TACTILE_JACOBIAN,         // the per-frame tactile Jacobians (k_tactile_jacobian, tsim_tactile_jacobian.hip): generic view only
-                TS_K_PARAM_JACOBIAN };         // the per-frame parameter Jacobians (k_param_jacobian, tsim_param_jacobian.hip): generic view only
+                TS_K_PARAM_JACOBIAN,           // the per-frame parameter Jacobians (k_param_jacobian, tsim_param_jacobian.hip): generic view only
+                TS_K_TACTILE_NORMAL };         // the tactile normal equations (k_tactile_normal, tsim_tactile_normal.hip): generic view only
 // the view of a launch: the generic kernels, a compiled-in model fully static, or its structure-static twin (parameters at run time)
 enum { TS_KM_GENERIC = 0, TS_KM_STATIC = 1, TS_KM_PARAM = 2 };
 using TsParamPusher = TsParam<TsStaticPusher>;
@@ -51,7 +53,7 @@ constexpr bool ts_instantiated(int kernel, int ms_nrm, bool fp32, bool policy, b
   if (policy != (kernel == TS_K_CLOSED_BACKWARD_Z) && kernel != TS_K_FORWARD && kernel != TS_K_BACKWARD) return false;
   if (policy && (nrm != 8 || expj)) return false;
   if (ms_nrm == 0) return !default_opts && kernel != TS_K_FRAME_RECORDS;
-  if (kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_FRAME_JACOBIAN || kernel == TS_K_TACTILE_JACOBIAN || kernel == TS_K_PARAM_JACOBIAN || nrm != ms_nrm || expj) return false;
+  if (kernel == TS_K_PARAM_GRAD || kernel == TS_K_PARAM_GRAD_BODY || kernel == TS_K_TANGENT || kernel == TS_K_TANGENT_BODY || kernel == TS_K_FRAME_JACOBIAN || kernel == TS_K_TACTILE_JACOBIAN || kernel == TS_K_PARAM_JACOBIAN || kernel == TS_K_TACTILE_NORMAL || nrm != ms_nrm || expj) return false;
   if (default_opts) return kernel == TS_K_FORWARD && fp32 && lpe == 16;
   if (policy || kernel == TS_K_DEBUG_EVAL) return fp32 && lpe == 16;
   return fp32 || lpe != 16;
@@ -67,6 +69,7 @@ template <class R, int NRM, bool EXPJ, int LPE, bool SRC> __global__ void __laun
 template <class R, int NRM, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_frame_jacobian(FjArgs<R> a);      // tsim_frame_jacobian.hip
 template <class R, int NRM, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_tactile_jacobian(TjArgs<R> a);      // tsim_tactile_jacobian.hip
 template <class R, int NRM, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_param_jacobian(PjArgs<R> a);      // tsim_param_jacobian.hip
+template <class R, int NRM, bool EXPJ, int LPE> __global__ void __launch_bounds__(TS_WAVE) k_tactile_normal(TnArgs<R> a);      // tsim_tactile_normal.hip
 
 template <int N> using TsInt = std::integral_constant<int, N>;
 template <bool B> using TsBool = std::integral_constant<bool, B>;
@@ -98,6 +101,7 @@ template <class MS, bool POLICY, class R> struct TsLaunch {
   static bool run(const TsPlan& p, hipStream_t st, const FjArgs<R>& a);
   static bool run(const TsPlan& p, hipStream_t st, const TjArgs<R>& a);
   static bool run(const TsPlan& p, hipStream_t st, const PjArgs<R>& a);
+  static bool run(const TsPlan& p, hipStream_t st, const TnArgs<R>& a);
   static bool run_tangent_src(const TsPlan& p, hipStream_t st, const TanArgs<R>& a);      // TS_K_TANGENT with a.src given: k_tangent_src (a member of its own: instantiated in tsim_tangent_body.hip)
   static bool run_closed_tangent(const TsPlan& p, hipStream_t st, const TanClosedArgs<R>& a);      // TS_K_CLOSED_TANGENT, SRC = (a.src given) (instantiated in tsim_tangent_closed.hip)
 };
@@ -151,6 +155,9 @@ template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(cons
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const PjArgs<R>& a) {
   return shape<TS_K_PARAM_JACOBIAN>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_param_jacobian<R, nrm, expj, lpe>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
 }
+template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run(const TsPlan& p, hipStream_t st, const TnArgs<R>& a) {
+  return shape<TS_K_TACTILE_NORMAL>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_tactile_normal<R, nrm, expj, lpe>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
+}
 template <class MS, bool POLICY, class R> bool TsLaunch<MS, POLICY, R>::run_tangent_src(const TsPlan& p, hipStream_t st, const TanArgs<R>& a) {
   return shape<TS_K_TANGENT>(p, [&](auto nrm, auto expj, auto lpe) { hipLaunchKernelGGL((k_tangent_src<R, nrm, expj, lpe>), dim3(p.grid), dim3(TS_WAVE), p.lds, st, a); });
 }
@@ -169,7 +176,7 @@ template <bool POLICY, class R, class A, class... Z> bool ts_launch(const TsPlan
 }
 // instantiated in their own units: tsim_static_pusher.hip, tsim_param_pusher.hip, their _policy twins, tsim_param_grad.hip, tsim_param_grad_body.hip,
 // tsim_closed_backward_z.hip, tsim_tangent.hip, tsim_tangent_body.hip, tsim_tangent_closed.hip, tsim_frame_jacobian.hip, tsim_tactile_jacobian.hip,
-// tsim_param_jacobian.hip
+// tsim_param_jacobian.hip, tsim_tactile_normal.hip
 extern template struct TsLaunch<TsStaticPusher, false, float>;
 extern template struct TsLaunch<TsStaticPusher, false, double>;
 extern template struct TsLaunch<TsStaticPusher, true, float>;
@@ -192,6 +199,8 @@ extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_
 extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const TjArgs<double>&);
 extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const PjArgs<float>&);
 extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const PjArgs<double>&);
+extern template bool TsLaunch<void, false, float>::run(const TsPlan&, hipStream_t, const TnArgs<float>&);
+extern template bool TsLaunch<void, false, double>::run(const TsPlan&, hipStream_t, const TnArgs<double>&);
 extern template bool TsLaunch<void, false, float>::run_tangent_src(const TsPlan&, hipStream_t, const TanArgs<float>&);
 extern template bool TsLaunch<void, false, double>::run_tangent_src(const TsPlan&, hipStream_t, const TanArgs<double>&);
 extern template bool TsLaunch<void, false, float>::run_closed_tangent(const TsPlan&, hipStream_t, const TanClosedArgs<float>&);

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import capi
+from ..model import blob as _blob
 from ..model.compiler import CompiledModel, load_model
 
 
@@ -326,6 +327,39 @@ class BatchSim:
         capi.check(capi.lib().tsim_param_jacobians(self._h, T, int(num_steps), ncols, carr, _ptr(slots), _ptr(o.get("E")), _ptr(o.get("Ft")), self._stream()))
         return o
 
+    def tactile_normal_equations(self, num_frames, num_steps, weight=None, residual=None, with_params=False, tactile_mask=None):
+        """The information form of the tactile block of the newest num_frames env-steps (num_steps sub-steps each) in one launch (include/tsim.h
+        tsim_tactile_normal_equations): a dict of N [n_masked, B, Z, Z] = H^T W H and, with `residual`, n [n_masked, B, Z] = H^T W r, for
+        H = [C_f | F_f] — C_f of tactile_jacobians, F_f the dense form of param_jacobians' Ft (with_params: column 2 ndof_r + 4 s + k is field k
+        = kn, kt, mu, damping of sensor s), Z = 2 ndof_r + (4 nsensor if with_params) — without C_f or F_f being stored.  weight [ndof_tactile]:
+        the diagonal of W, shared by all environments and frames (None: ones; negative or non-finite values are the caller's business);
+        residual [n_masked, B, ndof_tactile].  Both must be on the batch's device in its dtype and contiguous.  tactile_mask (bool[T]) as in
+        tactile_jacobians; a mask without a masked frame is refused.  N is exactly symmetric; a frame without a loaded taxel gives zeros, a sensor
+        without one zero parameter rows and columns.  The tape, the state and the carried adjoint are left as they are; a frame's bits do not
+        depend on num_frames, the mask or the batch size, the state block's neither on with_params nor on residual.
+        Size: Z^2 + Z reals per environment and masked frame — TactilePush with parameters, fp32: 1 368 bytes (Ct and Ft: 27 300)."""
+        T = int(num_frames)
+        ntac = self.ndof_tactile
+        for name, t in (("weight", weight), ("residual", residual)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != self.dtype or not t.is_contiguous():
+                raise ValueError("tactile_normal_equations: %s must be a contiguous %s tensor on %s" % (name, self.dtype, self.device))
+        slots, nm = self._tactile_slots(T, tactile_mask)
+        if nm < 1:
+            raise ValueError("tactile_normal_equations: the mask has no masked frame")
+        if weight is not None and tuple(weight.shape) != (ntac,):
+            raise ValueError("tactile_normal_equations: weight: expected shape [%d], got %s" % (ntac, tuple(weight.shape)))
+        if residual is not None and tuple(residual.shape) != (nm, self.B, ntac):
+            raise ValueError("tactile_normal_equations: residual: expected shape [%d, %d, %d], got %s" % (nm, self.B, ntac, tuple(residual.shape)))
+        Z = 2 * self.ndof_r + (4 * int(self.model.I[_blob.TSIM_IH_NSENSOR]) if with_params else 0)
+        o = {"N": torch.empty((nm, self.B, Z, Z), device=self.device, dtype=self.dtype)}
+        if residual is not None:
+            o["n"] = torch.empty((nm, self.B, Z), device=self.device, dtype=self.dtype)
+        capi.check(capi.lib().tsim_tactile_normal_equations(self._h, T, int(num_steps), _ptr(slots), int(bool(with_params)), _ptr(weight), _ptr(residual),
+                                                            _ptr(o["N"]), _ptr(o.get("n")), self._stream()))
+        return o
+
     def get_state(self):
         q, qd =self.empty(self.ndof_r), self.empty(self.ndof_r)
         capi.check(capi.lib().tsim_get_state(self._h, _ptr(q), _ptr(qd), self._stream()))
@@ -487,4 +521,12 @@ class BatchSim:
         columns selected nor on the outputs asked for"""
         out = (C.c_int32 * 4)()
         capi.check(capi.lib().tsim_param_jacobians_launch_info(self._h, out))
+        return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}
+
+    def tactile_normal_equations_launch_info(self, with_params=False):
+        """launch_info() of a tactile_normal_equations call (include/tsim.h tsim_tactile_normal_equations_launch_info): blocks PER FRAME; its
+        lanes per environment may be wider than the batch's, where a block would not hold every slot's records, sums and row tile; they depend
+        on with_params and on nothing else of a call"""
+        out = (C.c_int32 * 4)()
+        capi.check(capi.lib().tsim_tactile_normal_equations_launch_info(self._h, int(bool(with_params)), out))
         return {"lds_bytes": out[0], "threads": out[1], "blocks": out[2], "lanes_per_env": out[3]}

@@ -73,6 +73,7 @@ HIP_UNITS = [("tsim_hip.hip", []), ("tsim_static_pusher.hip", ["-ffinite-math-on
              ("tsim_frame_jacobian.hip", []),                                                     # the per-frame transition Jacobians (k_frame_jacobian, tsim_frame_jacobians): generic flags, a unit of its own likewise
              ("tsim_tactile_jacobian.hip", []),                                                   # the per-frame tactile Jacobians (k_tactile_jacobian, tsim_tactile_jacobians): generic flags, a unit of its own likewise
              ("tsim_param_jacobian.hip", []),                                                     # the per-frame parameter Jacobians (k_param_jacobian, tsim_param_jacobians): generic flags, a unit of its own likewise
+             ("tsim_tactile_normal.hip", []),                                                     # the tactile normal equations (k_tactile_normal, tsim_tactile_normal_equations): generic flags, a unit of its own likewise
              ("tsim_model.cpp", ["-ffp-contract=off"])]                                         # host only: the model loader (include/tsim_model.h); plain double arithmetic, no contraction
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC"]      # units that are not .hip: no device code
 

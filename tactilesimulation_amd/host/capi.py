@@ -45,6 +45,8 @@ _SIGS = {
     "tsim_tactile_jacobians_launch_info": (C.c_int, [_vp, _ip]),
     "tsim_param_jacobians": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _vp, _vp, _vp, _vp]),
     "tsim_param_jacobians_launch_info": (C.c_int, [_vp, _ip]),
+    "tsim_tactile_normal_equations": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "tsim_tactile_normal_equations_launch_info": (C.c_int, [_vp, C.c_int, _ip]),
     "tsim_last_adjoint_launch": (C.c_int, [_vp, _ip]),
     "tsim_set_lanes_per_env": (C.c_int, [_vp, C.c_int]),
     "tsim_kernel_timing": (C.c_int, [_vp, C.c_int]), "tsim_kernel_times": (C.c_int, [_vp, C.POINTER(C.c_double), _ip]),

@@ -464,9 +464,16 @@ const char* tsim_kernel_variant(const tsim_batch* b);
  * from that trial point alone.  A slot whose own environment is finished evaluates it in the same round; if the trial is committed, its environment
  * starts the next sub-step from that evaluation: one round per sub-step while a finished slot shares the wavefront.  Fused compiled-in BDF1 models,
  * free-running launches that record a tape.  Exact, as TSIM_OPT_TRIAL_HELPERS is (tests/test_gpu_predictor_helpers.py); tsim_last_helper_trials also
- * counts the predictors taken over.  It is no part of TSIM_OPT_ALL_DEFAULT: the instantiations read it at run time. */
+ * counts the predictors taken over.  It is no part of TSIM_OPT_ALL_DEFAULT: the instantiations read it at run time.
+ * TSIM_OPT_ADJOINT_PREPASS (set: 0 | 1, default 1; environment variable TSIM_NO_ADJOINT_PREPASS=1 at creation: 0)  tsim_backward_episode of a fused
+ * compiled-in model (fp32, 16 lanes per environment, BDF1, no parameter gradient set) computes the frames' seed partials — (dvar/dq)^T w_var +
+ * (dtac/dq)^T w_tac and (dtac/dqd)^T w_tac at each frame's taped final state — in a pass of its own over (frame, environment) items,
+ * k_adjoint_seeds, and the adjoint kernel (k_backward_pre) adds them instead of evaluating the tactile law inside its serial chain.  Same stream,
+ * same results bit for bit (tests/test_gpu_adjoint_prepass.py); the pass's buffer, tape capacity x B x 2 ndof_r reals, is allocated with the
+ * batch (if that fails the batch keeps the in-kernel path).  tsim_get_option reads whether the most recent adjoint launch took the path.  It is no
+ * part of TSIM_OPT_ALL_DEFAULT. */
 enum { TSIM_OPT_PAIR_CULL = 1, TSIM_OPT_VALUE_TRIALS = 2, TSIM_OPT_TRIAL_HELPERS = 3, TSIM_OPT_VALUE_FIRST = 4, TSIM_OPT_CROSS_KINKS = 5, TSIM_OPT_EVAL_BUDGET = 6,
-       TSIM_OPT_ALL_DEFAULT = 7, TSIM_OPT_FRAME_RECORDS = 8, TSIM_OPT_FORWARD_SPLIT = 9, TSIM_OPT_PREDICTOR_HELPERS = 10 };
+       TSIM_OPT_ALL_DEFAULT = 7, TSIM_OPT_FRAME_RECORDS = 8, TSIM_OPT_FORWARD_SPLIT = 9, TSIM_OPT_PREDICTOR_HELPERS = 10, TSIM_OPT_ADJOINT_PREPASS = 11 };
 int tsim_set_option(tsim_batch* b, int option, int value);
 int tsim_get_option(const tsim_batch* b, int option);
 

@@ -124,6 +124,9 @@ struct tsim_batch {
   DevBuf pg_slots;
   // diagnostics (tsim_last_adjoint_launch): the kernel of the most recent adjoint launch (TSIM_ADJ_*, -1: none yet) and the parameter passes behind it
   int adj_kernel = -1, adj_passes = 0;
+  // the seed pre-pass of the fused episode adjoint (tsim_adjoint_pre.h; tsim_set_option TSIM_OPT_ADJOINT_PREPASS, TSIM_NO_ADJOINT_PREPASS=1 at creation: off):
+  // its result [cap][B][2 nr], allocated with the tape (a batch whose allocation failed keeps the in-kernel path), and whether the last adjoint launch took the path
+  int adj_pre = 1, adj_pre_ran = 0; DevBuf sseed;
   // tsim_kernel_timing: HIP events around every launch of the simulation kernels, on the stream they are launched on
   int kt_on = 0;
   std::vector<KtPair> kt;           // pairs recorded since the last tsim_kernel_times

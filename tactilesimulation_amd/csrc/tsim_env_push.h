@@ -201,6 +201,7 @@ static int push_closed_backward_t(tsim_batch* b, const tsim_push_policy* pol, co
   if (!ts_launch<true, R>(ts_plan(b, b->dLdp ? TS_K_CLOSED_BACKWARD_Z : TS_K_BACKWARD, true, 0), st, a, (R*)b->zbuf)) return fail("no closed-loop k_backward instantiation for the launch plan");
   HIPCHK(hipGetLastError());
   b->adj_kernel = b->dLdp ? TSIM_ADJ_CLOSED_BACKWARD_Z : TSIM_ADJ_BACKWARD;
+  b->adj_pre_ran = 0;      // (the closed loop's tactile seed is produced inside the chain: no seed pre-pass, TSIM_OPT_ADJOINT_PREPASS reads 0)
   if (!b->dLdp) { b->adj_passes = 0; return 0; }
   // The contact pass's tactile seeds: frame f's tactile output is what frame f + 1's policy call observed, and the kernel above left its adjoint in
   // dobs_tac[f + 1] (k_backward reads the same row: tsim_kernels_backward.h); nothing observes the last frame's.  Slot f of the table is row f of

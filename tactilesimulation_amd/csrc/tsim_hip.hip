@@ -27,6 +27,7 @@
 #include "tsim_kernels.h"
 #include "tsim_param_grad.h"
 #include "tsim_launch.h"
+#include "tsim_adjoint_pre.h"
 #include "tsim_batch.h"      // the batch, the error text, the device guard, the precision dispatch, the owned buffers (host only)
 
 // ================================================================================================ LPT ordering
@@ -1009,7 +1010,14 @@ static int launch_backward(tsim_batch* b, int n, int seed_stride, int frames, co
     // with the parameter pass: the same variant's SAVEZ twin (z of every sub-step).  TSIM_BWD_LPE at creation (A/B): another launch shape for
     // the adjoint kernel (the tape does not depend on it)
     const TsPlan plan = ts_plan(b, b->dLdp ? TS_K_BACKWARD_Z : TS_K_BACKWARD, false, b->ab_bwd_lpe);
-    if (!ts_launch<false, R>(plan, st, a, (R*)b->zbuf)) return fail("no k_backward instantiation for the launch plan");
+    // An episode launch of a fused compiled-in view (fp32, 16 lanes, BDF1; no parameter gradient): the frames' seed partials by k_adjoint_seeds, then
+    // k_backward_pre, which reads them (tsim_adjoint_pre.h) — both on this stream and inside this timing scope: k_backward's time stays the whole adjoint side
+    b->adj_pre_ran = 0;
+    if constexpr (std::is_same<R, float>::value) {
+      if (b->adj_pre && b->sseed && frames == 1 && !b->dLdp && plan.fused && plan.lpe == 16 && b->I[TSIM_IH_INTEGRATOR] != 2 &&
+          ts_adjoint_pre_launch(plan, st, a, (float*)b->sseed, b->nfrec)) b->adj_pre_ran = 1;
+    }
+    if (!b->adj_pre_ran && !ts_launch<false, R>(plan, st, a, (R*)b->zbuf)) return fail("no k_backward instantiation for the launch plan");
   }
   HIPCHK(hipGetLastError());
   b->adj_kernel = b->dLdp ? TSIM_ADJ_BACKWARD_Z : TSIM_ADJ_BACKWARD;
@@ -1260,6 +1268,13 @@ int tsim_batch_create(const int32_t* I, const double* F, int B, int tape_capacit
   if (hipMemset(b->tape, 0, tape_bytes) != hipSuccess || hipMemset(b->lamq, 0, (size_t)2 * B * nr * b->esz) != hipSuccess ||
       hipMemset(b->lamv, 0, (size_t)2 * B * nr * b->esz) != hipSuccess) { tsim_batch_destroy(b); return fail("hipMemset failed"); }
   if (upload_model(b, nullptr)) { tsim_batch_destroy(b); return 1; }
+  // the seed pre-pass's buffer [cap][B][2 nr] (tsim_adjoint_pre.h), for a batch that can take the path: here, never at launch.  A failed allocation
+  // is no error: the batch keeps the in-kernel path (TSIM_OPT_ADJOINT_PREPASS reads 0)
+  b->adj_pre = getenv("TSIM_NO_ADJOINT_PREPASS") ? 0 : 1;
+  if (b->adj_pre && b->tape_k && dtype == TSIM_F32 && tape_capacity > 0 && hipMalloc(&b->sseed, (size_t)tape_capacity * B * 2 * nr * b->esz) != hipSuccess) {
+    (void)hipGetLastError();
+    b->adj_pre = 0;
+  }
   // the side stream of the split forward launch (launch_forward; a split has 64 blocks or more).  Non-blocking: it is ordered against the caller's
   // stream by its two events alone — the caller's may be the null stream, which every blocking stream waits for
   if (B >= 64 && !getenv("TSIM_NO_FORWARD_SPLIT")) {
@@ -1355,6 +1370,7 @@ int tsim_set_option(tsim_batch* b, int option, int value) {
   if (option == TSIM_OPT_TRIAL_HELPERS) { b->trial_helpers = value != 0; return 0; }
   if (option == TSIM_OPT_VALUE_FIRST) { b->value_first = value != 0; return 0; }
   if (option == TSIM_OPT_PREDICTOR_HELPERS) { b->pred_helpers = value != 0; return 0; }
+  if (option == TSIM_OPT_ADJOINT_PREPASS) { b->adj_pre = value != 0; return 0; }
   return fail("set_option: unknown option " + std::to_string(option));
 }
 int tsim_get_option(const tsim_batch* b, int option) {
@@ -1368,6 +1384,7 @@ int tsim_get_option(const tsim_batch* b, int option) {
   if (option == TSIM_OPT_FRAME_RECORDS) return b->last_frame_rec;
   if (option == TSIM_OPT_FORWARD_SPLIT) return b->last_fwd_split;
   if (option == TSIM_OPT_PREDICTOR_HELPERS) return b->pred_helpers;
+  if (option == TSIM_OPT_ADJOINT_PREPASS) return b->adj_pre_ran;
   return -1;
 }
 int tsim_set_solver_options(tsim_batch* b, int cross_kinks, int eval_budget) {

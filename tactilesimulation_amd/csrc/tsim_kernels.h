@@ -968,12 +968,12 @@ __device__ __forceinline__ void output_vjp(const Ctx<R>& c, int lane, const R* w
 // sched_barrier in the body).
 template <class R, int NRM, bool EXPJ, int LPE, bool POLICY = false, class MS = void>
 __global__ void TS_KLB_BWD k_backward(BwdArgs<R> a) {
-  constexpr bool SAVEZ = false; R* const zsave = nullptr;
+  constexpr bool SAVEZ = false, PRE = false; R* const zsave = nullptr; const R* const sseed = nullptr;
 #include "tsim_kernels_backward.h"
 }
 template <class R, int NRM, bool EXPJ, int LPE, bool POLICY = false, class MS = void>
 __global__ void TS_KLB_BWD k_backward_z(BwdArgs<R> a, R* zsave) {
-  constexpr bool SAVEZ = true;
+  constexpr bool SAVEZ = true, PRE = false; const R* const sseed = nullptr;
 #include "tsim_kernels_backward.h"
 }
 // ... and the SAVEZ twin of the CLOSED-LOOP adjoint kernel (k_backward's POLICY instantiations; tsim_push_closed_backward while a table-gradient
@@ -982,7 +982,7 @@ __global__ void TS_KLB_BWD k_backward_z(BwdArgs<R> a, R* zsave) {
 // (tsim_launch.h ts_instantiated, tests/test_capi_symbols.py), and this one is counted beside it like k_forward_fr and k_frame_records.
 template <class R, int NRM, bool EXPJ, int LPE, class MS = void>
 __global__ void TS_KLB_BWD k_closed_backward_z(BwdArgs<R> a, R* zsave) {
-  constexpr bool POLICY = true, SAVEZ = true;
+  constexpr bool POLICY = true, SAVEZ = true, PRE = false; const R* const sseed = nullptr;
 #include "tsim_kernels_backward.h"
 }
 

@@ -2,6 +2,8 @@
 // SAVEZ twin k_closed_backward_z (POLICY fixed to true) (tsim_kernels.h), which differ only in `SAVEZ` (a constexpr bool) and `zsave`.  Textual inclusion rather than a shared device function: k_backward must stay the
 // kernel it was, code bytes and registers (a body behind a function call boundary, even inlined, schedules differently; host/buildhash.py's
 // kernel table shows it).  Not a header of its own: it has no meaning outside those function bodies.
+// `PRE` (a constexpr bool like SAVEZ, with `sseed`): on in k_backward_pre alone (tsim_adjoint_pre.h), the twin a fused episode launch runs behind
+// k_adjoint_seeds: a seeded sub-step adds the two vectors that pass wrote for its frame instead of running ts_static_output_vjp in the chain.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   R* lds = reinterpret_cast<R*>(smem_raw);
   constexpr int NS = TS_WAVE / LPE;
@@ -55,6 +57,14 @@
       for (int i = 0; i < NHL; ++i) { const int e = lane + i * LPE; pK[i] = (a.tk && e < nr * nr) ? r1[oK + e] : R(0); }
     }
   }
+  // PRE: the seed partials of a frame, sseed[frame][env][sq (nr) | sv (nr)] (k_adjoint_seeds), fetched one iteration ahead like the record
+  [[maybe_unused]] R psq = R(0), psv = R(0);
+  if constexpr (PRE) {
+    if (a.n % a.seed_stride == 0 && lane < nr) {      // sub-step n - 1 ends a frame
+      const R* sp = sseed + ((size_t)((a.n - 1) / a.seed_stride) * a.B + env) * (2 * nr);
+      psq = sp[lane]; psv = sp[nr + lane];
+    }
+  }
   for (int j = a.n - 1; j >= 0; --j) {
     const int t = a.t_end - (a.n - 1 - j);
     const bool bdf2 = bdf2_model && t >= 2;
@@ -74,6 +84,13 @@
       for (int i = 0; i < NHL; ++i) { const int e = lane + i * LPE; if (e < nr * nr) KT[e] = pK[i]; }
     }
     TS_STAMP(c);
+    [[maybe_unused]] const R sq_now = psq, sv_now = psv;
+    if constexpr (PRE) {
+      if (j > 0 && j % a.seed_stride == 0 && lane < nr) {      // the next iteration's sub-step j - 1 ends a frame
+        const R* sp = sseed + ((size_t)((j - 1) / a.seed_stride) * a.B + env) * (2 * nr);
+        psq = sp[lane]; psv = sp[nr + lane];
+      }
+    }
     if (j > 0) {                                      // next iteration: sub-step t - 1
       const R* r1 = a.tape + ((size_t)(t - 1) * a.B + env) * REC;
       const R* r0 = a.tape + ((size_t)(t - 2) * a.B + env) * REC;
@@ -110,7 +127,8 @@
       TS_SYNC();
       const R* wtac_ = (a.df_dtac && ntac3 && tslot >= 0) ? a.df_dtac + sot * ntac3 : nullptr;
       if (POLICY) wtac_ = (pol_have && a.pol.mode == TSIM_PUSH_OBS_TACTILE) ? a.pol.dobs_tac + ((size_t)(fr + 1) * a.B + env) * PP_NTAC : nullptr;   // tactile part (frame fr + 1's observation)
-      if constexpr (kFused) ts_static_output_vjp<R, LPE, MS>(c, lane, (a.df_dvar && nvar3) ? a.df_dvar + so * nvar3 : nullptr, wtac_);
+      if constexpr (PRE) { if (lane < nr) { c.lamq[lane] += sq_now; c.lamv[lane] += sv_now; } TS_SYNC(); }
+      else if constexpr (kFused) ts_static_output_vjp<R, LPE, MS>(c, lane, (a.df_dvar && nvar3) ? a.df_dvar + so * nvar3 : nullptr, wtac_);
       else output_vjp<LPE>(c, lane, (a.df_dvar && nvar3) ? a.df_dvar + so * nvar3 : nullptr, wtac_);
     }
     TS_STAMP(c);

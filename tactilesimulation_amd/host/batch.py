@@ -469,6 +469,7 @@ class BatchSim:
     OPT_PAIR_CULL, OPT_VALUE_TRIALS, OPT_TRIAL_HELPERS, OPT_VALUE_FIRST, OPT_CROSS_KINKS, OPT_EVAL_BUDGET, OPT_ALL_DEFAULT, OPT_FRAME_RECORDS = 1, 2, 3, 4, 5, 6, 7, 8
     OPT_FORWARD_SPLIT = 9      # read-only: the newest forward launch went out split by LPT rank (include/tsim.h)
     OPT_PREDICTOR_HELPERS = 10      # finished slots evaluate a live slot's next predictor ahead (include/tsim.h; TSIM_NO_PREDICTOR_HELPERS=1 at creation: off)
+    OPT_ADJOINT_PREPASS = 11      # set: the episode adjoint's seed pre-pass on / off; get: the last adjoint launch took it (include/tsim.h; TSIM_NO_ADJOINT_PREPASS=1 at creation: off)
 
     def set_option(self, option, value):
         """include/tsim.h tsim_set_option (TSIM_OPT_*)."""

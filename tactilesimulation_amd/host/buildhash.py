@@ -74,6 +74,7 @@ HIP_UNITS = [("tsim_hip.hip", []), ("tsim_static_pusher.hip", ["-ffinite-math-on
              ("tsim_tactile_jacobian.hip", []),                                                   # the per-frame tactile Jacobians (k_tactile_jacobian, tsim_tactile_jacobians): generic flags, a unit of its own likewise
              ("tsim_param_jacobian.hip", []),                                                     # the per-frame parameter Jacobians (k_param_jacobian, tsim_param_jacobians): generic flags, a unit of its own likewise
              ("tsim_tactile_normal.hip", []),                                                     # the tactile normal equations (k_tactile_normal, tsim_tactile_normal_equations): generic flags, a unit of its own likewise
+             ("tsim_adjoint_pre.hip", ["-ffinite-math-only", "-fno-signed-zeros", "-O2"]),        # the episode adjoint's seed pre-pass and its chain kernel (k_adjoint_seeds, k_backward_pre): the static unit's flags, a unit of its own likewise
              ("tsim_model.cpp", ["-ffp-contract=off"])]                                         # host only: the model loader (include/tsim_model.h); plain double arithmetic, no contraction
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC"]      # units that are not .hip: no device code
 
@@ -162,6 +163,14 @@ def kernel_name(kernel, dtype, nr, has_exp, lanes, variant, policy=False, defaul
     # the two kernels of an episode launch that ends no frame inside the forward kernel (csrc/tsim_hip.hip launch_forward; fused compiled-in models):
     # k_frame_records, the pass that writes the frames' outputs from the tape, at every shape the view's k_forward has; k_forward_fr, the forward
     # kernel with that switch and every option's default as constants, where the TsDefaultOpts<> twin is (fp32, 16 lanes)
+    # the episode adjoint with the seed pre-pass (csrc/tsim_adjoint_pre.h; fp32, 16 lanes, a compiled-in model): the pass and the chain kernel behind it
+    if kernel == "k_adjoint_seeds":
+        back = {"static:pusher": 2, "param:pusher": 4}[variant]
+        return ("_Z15k_adjoint_seedsI%sLi%dE%sEv7BwdArgsIT_EPS%d_" % (r[0], lpe, ms[0], back), "k_adjoint_seeds<%s, LPE=%d, %s>" % (r[1], lpe, ms[1]))
+    if kernel == "k_backward_pre":
+        back = {"static:pusher": 2, "param:pusher": 4}[variant]
+        return ("_Z14k_backward_preI%sLi%dELb%dELi%dE%sEv7BwdArgsIT_EPKS%d_" % (r[0], nrm, int(expj), lpe, ms[0], back),
+                "k_backward_pre<%s, NRM=%d, EXPJ=%s, LPE=%d, %s>" % (r[1], nrm, str(expj).lower(), lpe, ms[1]))
     if kernel == "k_frame_records":
         return ("_Z15k_frame_recordsI%sLi%dE%sEv7FwdArgsIT_Ei10TsSubRange" % (r[0], lpe, ms[0]), "k_frame_records<%s, LPE=%d, %s>" % (r[1], lpe, ms[1]))
     if kernel == "k_forward_fr":
